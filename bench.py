@@ -351,6 +351,38 @@ def lbfgs_still_moving(opt, expect_iters, what):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # all of --dump-outputs together
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32 (float64 stays float64).  When
+    they would exceed `limit` together, the largest ones are replaced by a fixed sample of their flattened elements: the same
+    indices for the same shape (numpy Generator(DUMP_SAMPLE_SEED), drawn without replacement, ascending), written as
+    <name>_sample.npy, so two builds run with the same arguments can be compared element for element.  Returns {file: shape}."""
+    import numpy as np
+    outs = {}
+    for name, t in arrays.items():
+        v = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        outs[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    budget, plan = limit, {}
+    for i, name in enumerate(sorted(outs, key=lambda k: outs[k].nbytes)):  # small arrays whole, the largest ones share what is left
+        v = outs[name]
+        share = budget // (len(outs) - i)
+        if v.nbytes > share:
+            k = share // v.itemsize
+            if k < 1:
+                raise ValueError(f"bench.py --dump-outputs: no room left for {name} under {limit} bytes")
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(v.size, size=k, replace=False))
+            name, v = name + "_sample", v.reshape(-1)[idx]
+        plan[name] = v
+        budget -= v.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in plan.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name + ".npy": list(v.shape) for name, v in plan.items()}
+
+
 def steady_rate(size, steps, optimizer="lbfgs", history=100, warmup=5):
     """iterations/s of one more single-image job at another size on this rank's GPU (the 512x512 figure north_star asks for
     next to the 1024x1024 headline): same construction as the main workload, history prefilled, graph replay."""
@@ -442,6 +474,9 @@ def main():
     ap.add_argument("--no_accuracy_probe", action="store_true", help="skip the in-run fp64 check of the timed convolution kernels")
     ap.add_argument("--repeats", type=int, default=5, help="further K-step regions timed after the headline one")
     ap.add_argument("--allow_fewer", action="store_true", help="with fewer than --gpus devices visible: run on those and report it")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0: the image after its move, the per-module "
+                         "losses and the total of its evaluation) as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--requested_gpus", type=int, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--_launched", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--_wait_for_go", action="store_true", help=argparse.SUPPRESS)
@@ -516,10 +551,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        opt.step()
+        last = opt.step()
     torch.cuda.synchronize()
     dist.barrier()
     mine = time.perf_counter() - t0
+    dumped = None
+    if a.dump_outputs and rank == 0:  # before the repeated regions move the image on and reuse the engine's loss buffers
+        slots, total = last
+        dumped = dump_outputs(a.dump_outputs, {"image": opt.x, "loss_slots": slots, "loss_total": total})
     # (every rank checks its own optimiser: a stop flag raised inside the timed region voids the rate)
     moving = lbfgs_still_moving(opt, prefill + a.warmup + a.steps, "the headline") if a.optimizer == "lbfgs" else None
     elapsed = dist.max_over_ranks(mine)
@@ -703,6 +742,8 @@ def main():
                                             "max": round(max(repeats) / a.steps * 1e3, 4)},
                             "note": "the K-step timed region repeated after the headline region (which stays `value`), each "
                                     "bracketed by barrier + synchronize, max over ranks"}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": os.path.abspath(a.dump_outputs), "files": dumped}
     if a.requested_gpus:
         out["requested_gpus"] = a.requested_gpus
         out["note_gpus"] = f"{a.requested_gpus} GPUs requested, {world} visible: ran on {world} (--allow_fewer)"

@@ -412,3 +412,26 @@ def test_bench_line_refuses_a_stopped_optimiser():
     opt.state = State(n_iter=290, history_len=100, stopped=False, gtd=-1.0, t=1.0)
     with pytest.raises(RuntimeError):
         bench.lbfgs_still_moving(opt, 305, "the test")
+
+
+def test_bench_dump_outputs_stays_under_its_limit_and_samples_the_same_elements(tmp_path):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): float32 .npy files, small arrays whole, an array too large for the byte limit
+    replaced by a seeded sample of its elements - the same indices on every run, so two builds' dumps compare element for element."""
+    import bench
+    import numpy as np
+    image = torch.arange(3 * 64 * 64, dtype=torch.float32).reshape(1, 3, 64, 64)
+    arrays = {"image": image, "loss_slots": torch.tensor([1.0, 2.0, 3.0]), "loss_total": torch.tensor([6.0], dtype=torch.float64)}
+    files = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert files == {"image.npy": [1, 3, 64, 64], "loss_slots.npy": [3], "loss_total.npy": [1]}
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, image.numpy())
+    assert np.load(tmp_path / "whole" / "loss_total.npy").dtype == np.float64
+
+    limit = 4096 + 3 * 4 + 8  # room for 1024 image elements next to the two small arrays
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    b = bench.dump_outputs(str(tmp_path / "b"), {k: v.clone() for k, v in arrays.items()}, limit=limit)
+    assert a == b == {"loss_total.npy": [1], "loss_slots.npy": [3], "image_sample.npy": [1024]}
+    sa, sb = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "b" / "image_sample.npy")
+    assert np.array_equal(sa, sb) and sa.dtype == np.float32
+    assert len(np.unique(sa)) == 1024 and np.all(np.diff(sa) > 0)  # distinct elements, in flat-index order
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in a) <= limit  # (128 B: the .npy header)
