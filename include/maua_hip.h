@@ -497,6 +497,38 @@ int maua_lbfgs_iterate(void* state, float* x, const float* grad, const float* lo
                        float tolerance_change, float tolerance_grad, maua_stream_t stream);
 int maua_lbfgs_status(const void* state, int64_t count, int history, float* out5, maua_stream_t stream);
 
+/* ---- optical flow for vid_img's temporal path: the reference's flow networks (flow.py:32-74, load.py:141-188) replaced by a
+ *      weight-free coarse-to-fine TV-L1 solver, and its occlusion / reliability mask (flow.py:77-137) ------------------------------
+ * Planes are fp32, row-major h x w, one plane per component.  Flow = 2 planes [u][v] in pixels, img1(x) ~ img2(x + flow(x)).
+ * Solver state = 6 planes [u1][u2][p11][p12][p21][p22]; fields = 3 planes [I1wx][I1wy][rho_c] ("Optical flow").
+ * Sizes: 1 <= h, w <= 65536, h * w <= 2^28.  maua_flow_levels (host only): pyramid levels for h x w, at most max_levels, the
+ * coarsest level's shorter side >= 16 (ceil halving).
+ * maua_flow_grey_u8: (h, w, 3) RGB bytes -> (0.299 R + 0.587 G) + 0.114 B.
+ * maua_flow_pyr_down: Gaussian (sigma 0.6 sqrt(3)) + 2x decimation -> ceil(h/2) x ceil(w/2), edge pixels replicated.
+ * maua_flow_warp_prep: fields of one warp from I0, I1 and the flow u (2 planes).
+ * maua_flow_tvl1_step: one TV-L1 iteration, state_in -> state_out.  maua_flow_tvl1_blocked: k (1..16) iterations in one launch,
+ * bit-identical to k launches of maua_flow_tvl1_step.  Both need state_in != state_out.
+ * maua_flow_median5: 5 x 5 median (edge replicated) of `planes` planes.  maua_flow_upsample: bilinear, half-pixel centres, x scale.
+ * maua_flow_consistency: the reference's check_consistency(flow1, flow2) as the PNG bytes it writes, (1 - r) * 255 (h, w >= 2);
+ * workspace maua_flow_consistency_workspace_bytes(h, w).
+ * maua_flow_tvl1: the whole estimate for one frame pair (grey, pyramids, `levels` levels x `warps` warps x `iters` iterations,
+ * block_k 0/1 = single-step kernel, 2..16 = blocked kernel with that k; same bits either way); workspace
+ * maua_flow_tvl1_workspace_bytes(h, w, levels) (0 = invalid).  Fixed launch sequence: capturable into a hipGraph. */
+int maua_flow_levels(int h, int w, int max_levels);
+int maua_flow_grey_u8(const uint8_t* rgb, float* out, int h, int w, maua_stream_t stream);
+int maua_flow_pyr_down(const float* in, float* out, int h, int w, maua_stream_t stream);
+int maua_flow_warp_prep(const float* i0, const float* i1, const float* u, float* fields, int h, int w, maua_stream_t stream);
+int maua_flow_tvl1_step(const float* fields, const float* state_in, float* state_out, int h, int w, maua_stream_t stream);
+int maua_flow_tvl1_blocked(const float* fields, const float* state_in, float* state_out, int h, int w, int k, maua_stream_t stream);
+int maua_flow_median5(const float* in, float* out, int h, int w, int planes, maua_stream_t stream);
+int maua_flow_upsample(const float* in, int ch, int cw, float* out, int h, int w, int planes, float scale, maua_stream_t stream);
+size_t maua_flow_consistency_workspace_bytes(int h, int w);
+int maua_flow_consistency(const float* flow1, const float* flow2, uint8_t* out, int h, int w, void* workspace, size_t workspace_bytes,
+                          maua_stream_t stream);
+size_t maua_flow_tvl1_workspace_bytes(int h, int w, int levels);
+int maua_flow_tvl1(const uint8_t* rgb1, const uint8_t* rgb2, float* flow, int h, int w, int levels, int warps, int iters, int block_k,
+                   void* workspace, size_t workspace_bytes, maua_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

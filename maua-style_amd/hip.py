@@ -128,6 +128,18 @@ SIGNATURES = {
     "maua_lbfgs_init": (c_i, [c_p, c_sz, c_i64, c_i, c_p]),
     "maua_lbfgs_iterate": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_f, c_f, c_f, c_p]),
     "maua_lbfgs_status": (c_i, [c_p, c_i64, c_i, c_p, c_p]),
+    "maua_flow_levels": (c_i, [c_i, c_i, c_i]),
+    "maua_flow_grey_u8": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "maua_flow_pyr_down": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "maua_flow_warp_prep": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
+    "maua_flow_tvl1_step": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
+    "maua_flow_tvl1_blocked": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "maua_flow_median5": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
+    "maua_flow_upsample": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_f, c_p]),
+    "maua_flow_consistency_workspace_bytes": (c_sz, [c_i, c_i]),
+    "maua_flow_consistency": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_flow_tvl1_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "maua_flow_tvl1": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
 }
 
 
@@ -1065,3 +1077,136 @@ class LbfgsState:
                "maua_lbfgs_status")
         n_iter, hlen, stopped, gtd, t = self._status.tolist()
         return dict(n_iter=int(n_iter), history_len=int(hlen), stopped=bool(stopped), gtd=gtd, t=t)
+
+
+# ------------------------------------------------------------------------------------------
+# optical flow (csrc/flow.hip): planes [component][h][w], fp32; frames (h, w, 3) uint8 RGB
+# ------------------------------------------------------------------------------------------
+FLOW_MAX_LEVELS = 8
+
+
+def _flow_dims_ok(h, w):
+    return 0 < h <= 1 << 16 and 0 < w <= 1 << 16 and h * w <= 1 << 28
+
+
+def flow_levels(h, w, max_levels=5):
+    """Pyramid levels for an h x w pair (maua_flow_levels, restated on the host): ceil halving while the coarser level's shorter
+    side stays >= 16, at most `max_levels`."""
+    if not _flow_dims_ok(h, w) or max_levels < 1:
+        return 0
+    n = 1
+    while n < max_levels and (h + 1) // 2 >= 16 and (w + 1) // 2 >= 16:
+        h, w, n = (h + 1) // 2, (w + 1) // 2, n + 1
+    return n
+
+
+def flow_tvl1_workspace_bytes(h, w, levels):
+    """Bytes of maua_flow_tvl1's workspace (the library's own formula, restated on the host): both grey pyramids, two solver states
+    (6 planes) and the fields (3 planes) at the finest size, a 2-plane scratch; every region 256-byte aligned.  0 = invalid."""
+    if not _flow_dims_ok(h, w) or not 1 <= levels <= FLOW_MAX_LEVELS or levels > flow_levels(h, w, levels):
+        return 0
+    a = lambda b: (b + 255) & ~255
+    total, lh, lw = 0, h, w
+    for _ in range(levels):
+        total += 2 * a(lh * lw * 4)
+        lh, lw = (lh + 1) // 2, (lw + 1) // 2
+    return total + 2 * a(6 * h * w * 4) + a(3 * h * w * 4) + a(2 * h * w * 4)
+
+
+def _u8(t, name, shape=None):
+    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+        raise HipError(f"{name}: expected a contiguous uint8 device tensor")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise HipError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.data_ptr()
+
+
+def flow_grey(rgb):
+    """(h, w, 3) uint8 RGB -> (h, w) fp32 grey, (0.299 R + 0.587 G) + 0.114 B."""
+    h, w = rgb.shape[:2]
+    out = torch.empty(h, w, dtype=torch.float32, device=rgb.device)
+    _check(lib().maua_flow_grey_u8(_u8(rgb, "rgb", (h, w, 3)), out.data_ptr(), h, w, _stream()), "maua_flow_grey_u8")
+    return out
+
+
+def flow_pyr_down(img):
+    """(h, w) -> (ceil(h/2), ceil(w/2)): Gaussian smoothing and 2x decimation."""
+    h, w = img.shape
+    out = torch.empty((h + 1) // 2, (w + 1) // 2, dtype=torch.float32, device=img.device)
+    _check(lib().maua_flow_pyr_down(_ptr(_f32(img, "img")), out.data_ptr(), h, w, _stream()), "maua_flow_pyr_down")
+    return out
+
+
+def flow_warp_prep(i0, i1, u, fields=None):
+    """Fields [I1wx][I1wy][rho_c] (3, h, w) of one warp at the flow u (2, h, w)."""
+    h, w = i0.shape
+    if tuple(i1.shape) != (h, w) or tuple(u.shape) != (2, h, w):
+        raise HipError("flow_warp_prep: shapes")
+    if fields is None:
+        fields = torch.empty(3, h, w, dtype=torch.float32, device=i0.device)
+    _check(lib().maua_flow_warp_prep(_ptr(_f32(i0, "i0")), _ptr(_f32(i1, "i1")), _ptr(_f32(u, "u")), _ptr(fields), h, w, _stream()),
+           "maua_flow_warp_prep")
+    return fields
+
+
+def flow_tvl1_step(fields, state, out=None, k=0):
+    """TV-L1 iterations on the state (6, h, w) = [u1, u2, p11, p12, p21, p22]: k = 0 one single-step launch, k >= 1 one launch of the
+    temporally blocked kernel running k iterations.  Returns the new state (a different tensor)."""
+    _, h, w = state.shape
+    if tuple(state.shape) != (6, h, w) or tuple(fields.shape) != (3, h, w):
+        raise HipError("flow_tvl1_step: shapes")
+    if out is None:
+        out = torch.empty_like(state)
+    if k == 0:
+        _check(lib().maua_flow_tvl1_step(_ptr(_f32(fields, "fields")), _ptr(_f32(state, "state")), _ptr(out), h, w, _stream()),
+               "maua_flow_tvl1_step")
+    else:
+        _check(lib().maua_flow_tvl1_blocked(_ptr(_f32(fields, "fields")), _ptr(_f32(state, "state")), _ptr(out), h, w, int(k), _stream()),
+               "maua_flow_tvl1_blocked")
+    return out
+
+
+def flow_median5(x):
+    """5 x 5 median of every plane of (p, h, w), edge pixels replicated."""
+    p, h, w = x.shape
+    out = torch.empty_like(x)
+    _check(lib().maua_flow_median5(_ptr(_f32(x, "x")), _ptr(out), h, w, p, _stream()), "maua_flow_median5")
+    return out
+
+
+def flow_upsample(x, h, w, scale=2.0):
+    """(p, ch, cw) -> (p, h, w): bilinear with half-pixel centres, values x scale."""
+    p, ch, cw = x.shape
+    out = torch.empty(p, h, w, dtype=torch.float32, device=x.device)
+    _check(lib().maua_flow_upsample(_ptr(_f32(x, "x")), ch, cw, _ptr(out), h, w, p, float(scale), _stream()), "maua_flow_upsample")
+    return out
+
+
+def flow_consistency(flow1, flow2):
+    """The reference's check_consistency(flow1, flow2) as the bytes of its PNG, (1 - r) * 255: flows as (2, h, w) planes [u][v]."""
+    _, h, w = flow1.shape
+    if tuple(flow1.shape) != (2, h, w) or tuple(flow2.shape) != (2, h, w):
+        raise HipError("flow_consistency: shapes")
+    need = lib().maua_flow_consistency_workspace_bytes(h, w)
+    ws = torch.empty(max(need, 1), dtype=torch.uint8, device=flow1.device)
+    out = torch.empty(h, w, dtype=torch.uint8, device=flow1.device)
+    _check(lib().maua_flow_consistency(_ptr(_f32(flow1, "flow1")), _ptr(_f32(flow2, "flow2")), out.data_ptr(), h, w, ws.data_ptr(), need,
+                                       _stream()), "maua_flow_consistency")
+    return out
+
+
+def flow_tvl1(rgb1, rgb2, levels, warps, iters, block_k, out=None, workspace=None):
+    """The whole TV-L1 estimate of one pair of (h, w, 3) uint8 RGB frames -> (2, h, w) flow [u][v] with rgb1(x) ~ rgb2(x + flow(x))."""
+    h, w = rgb1.shape[:2]
+    need = flow_tvl1_workspace_bytes(h, w, levels)
+    if need == 0:
+        raise HipError(f"flow_tvl1: {levels} levels for {h}x{w}")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rgb1.device)
+    if workspace.numel() < need:
+        raise HipError("flow_tvl1: workspace too small")
+    if out is None:
+        out = torch.empty(2, h, w, dtype=torch.float32, device=rgb1.device)
+    _check(lib().maua_flow_tvl1(_u8(rgb1, "rgb1", (h, w, 3)), _u8(rgb2, "rgb2", (h, w, 3)), _ptr(_f32(out, "out")), h, w, int(levels),
+                                int(warps), int(iters), int(block_k), workspace.data_ptr(), workspace.numel(), _stream()), "maua_flow_tvl1")
+    return out

@@ -1,10 +1,10 @@
 """Image pre/post-processing with the reference's conventions (reference load.py:21-137), without torchvision /
 skvideo (absent here): Caffe-style VGG input = BGR, 0..255, mean-subtracted.
 
-Video decoding and flow ESTIMATION (load.py:141-188) need ffmpeg binaries and the flow networks of the un-vendored
-submodules; they are outside this build.  `process_content_frames` reads a directory of frame images, and the flow
-files the reference caches (`.flo` fields, reliability PNGs; load.py:191-231) are consumed by `flow_warp_map` /
-`reliable_flow_weighting`.
+Video decoding (load.py:141-188) needs ffmpeg binaries and is outside this build: `process_content_frames` reads a
+directory of frame images.  The reference's flow networks (un-vendored submodules, downloaded weights) are replaced by the
+built-in TV-L1 estimator of flow.py (`--flow_models tvl1`, flow.write_flow_cache); the flow files the reference caches
+(`.flo` fields, reliability PNGs; load.py:191-231) are consumed by `flow_warp_map` / `reliable_flow_weighting`.
 """
 import os
 
@@ -131,8 +131,8 @@ def process_content_frames(content):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Precomputed optical flow.  Estimating flow (the reference's un-vendored flow networks) is out of
-# scope; consuming the files it leaves in <output_dir>/flow/ is not: Middlebury .flo fields and reliability PNGs.
+# Optical flow cache: Middlebury .flo fields and reliability PNGs in <output_dir>/flow/, as the reference's
+# flow networks leave them or as flow.write_flow_cache (--flow_models tvl1) writes them.
 # ---------------------------------------------------------------------------------------------------------
 FLO_MAGIC = 202021.25
 

@@ -8,9 +8,10 @@ content / styles / previous result, optional histogram matching before and after
 scale, PNG per scale.  `vid_img` is the reference's per-frame loop (style.py:145-311).  Without optical flow
 (BASELINE config 4) the frames are independent optimisations that share the network and the style targets, so they
 are block-partitioned over the ranks of a torchrun job (dist.py) - one RCCL broadcast of weights and style targets,
-no per-iteration collective, every rank writes its own frames.  With a precomputed flow cache (`.flo` fields and
-reliability PNGs under <output_dir>/flow, as the reference's flow networks leave them) the temporally consistent
-loop runs: warped previous result as initialisation and as pixel-level temporal target (sequential, one rank).
+no per-iteration collective, every rank writes its own frames.  With a flow cache (`.flo` fields and reliability PNGs
+under <output_dir>/flow, as the reference's flow networks leave them, or as `--flow_models tvl1` writes them with the
+built-in TV-L1 estimator, flow.py) the temporally consistent loop runs: warped previous result as initialisation and as
+pixel-level temporal target (sequential, one rank).
 `img_vid` (README of the reference: "not sure if this is actually working"; its driver fails in its own loader) follows the
 reference's intended flow with clips as directories of frames: optim.optimize's '_vid' branch - sliding windows of B
 frames with the cross-frame dynamic Gram term - is the part with reference parity (tests/golden/imgvid_S64.npz).
@@ -29,6 +30,7 @@ import torch.nn.functional as F
 
 import config
 import dist
+import flow
 import load
 import models
 import optim
@@ -174,8 +176,8 @@ def img_vid(args):
 def _vid_img_flow(args, output_dir, frames, style_images_big, content_size):
     """The reference's temporally consistent loop (style.py:153-305) over a PRECOMPUTED flow cache
     (`<output_dir>/flow/{forward,backward}_<prev>_<this>.flo` + `.png` reliability masks, as its flow networks leave them;
-    estimating flow is outside this build).  Frames depend on their predecessor (warped previous result = initialisation
-    and pixel-level temporal target), so this path is sequential: one rank runs it."""
+    `--flow_models tvl1` has flow.write_flow_cache estimate them first).  Frames depend on their predecessor (warped previous
+    result = initialisation and pixel-level temporal target), so this path is sequential: one rank runs it."""
     passes = max(1, args.passes_per_scale)
     prev_size = None
     for size_n, (current_size, num_iters) in enumerate(zip(args.image_sizes, args.num_iters)):
@@ -337,6 +339,12 @@ def vid_img(args):
     rank, _, world = dist.init()
     output_dir = args.output_dir + "/" + name(args.content) + "_" + "_".join([name(s) for s in args.style])
     frames = load.process_content_frames(args.content)
+    if args.temporal_weight > 0 and flow.uses_tvl1(args):
+        # --flow_models tvl1: rank 0 completes the flow cache (the reference estimates flow before anything else, style.py:148-149),
+        # then runs the temporally consistent loop below; the other ranks leave at once, as they do when a cache already exists
+        if rank != 0:
+            return
+        flow.write_flow_cache(flow.get_flow_model(args), args)
     if args.temporal_weight > 0 and glob.glob(output_dir + "/flow/*.flo"):
         # sequential job (every frame starts from its predecessor): rank 0 runs it, the other ranks of a torchrun launch
         # leave at once - no collective here, a barrier would time out (and hold the GPUs) while rank 0 works for hours
