@@ -529,6 +529,32 @@ size_t maua_flow_tvl1_workspace_bytes(int h, int w, int levels);
 int maua_flow_tvl1(const uint8_t* rgb1, const uint8_t* rgb2, float* flow, int h, int w, int levels, int warps, int iters, int block_k,
                    void* workspace, size_t workspace_bytes, maua_stream_t stream);
 
+/* ---- neural cellular automaton textures (the reference's NCA_train.py / NCA_gen.py, CA.forward lines 154-186) ----------------
+ * State x: (n, chn, h, w) fp32.  params: one flat fp32 buffer [w1 (hidden x 4 chn)][b1 (hidden)][w2 (chn x hidden)] (the 1x1
+ * Conv2d weights of the reference's CA without their unit taps); maua_nca_param_count(chn, hidden) floats, 0 = pair not built.
+ * Built pairs: chn/hidden = 12/96 (the reference's) and 16/128.  maua_nca_supported(n, chn, hidden, h, w) (host only): 1 <= n <= 65536,
+ * 1 <= h, w <= 16384, n h w <= 2^28, and a built pair.
+ * maua_nca_step: out = x + mask * W2 relu(W1 p(x) + b1), p = the circular per-channel perception, channel 4c + f = channel c under
+ *   filter f in (ident, sobel_x, sobel_x^T, lap).  mask: the explicit fp32 (n, h, w) `mask` when non-null; else
+ *   floor(u + rate) with rate = rate_map[y][x] ((h, w), nullable) or `rate`, and u in [0, 1) a stateless function of
+ *   (seed, step, b, y, x) on a 2^-24 grid ("Neural cellular automaton").  out != x.
+ * maua_nca_step_bwd: backward of one step for backpropagation through time: dx = g + perception^T(W1^T(relu'(a) W2^T(mask g)))
+ *   (g = dL/d out, the mask recomputed from the same arguments as the forward call; dx may alias g, not x), and the parameter
+ *   gradient of this step added to per-workgroup partial slots in `workspace` (maua_nca_bwd_workspace_bytes); first != 0 clears
+ *   the slots first (the last step of a chain, which a BPTT visits first).
+ * maua_nca_grad_finish: grad (param_count floats, the params layout) = the slots summed in fixed order; normalize != 0 then divides
+ *   each of w1, b1 and w2 by its own L2 norm + 1e-8 (NCA_train.py:229-230).  Same inputs, same bits: no float atomics. */
+int maua_nca_supported(int n, int chn, int hidden, int h, int w);
+int64_t maua_nca_param_count(int chn, int hidden);
+int maua_nca_step(const float* x, float* out, const float* params, int n, int chn, int hidden, int h, int w, float rate,
+                  const float* rate_map, const float* mask, uint64_t seed, int64_t step, maua_stream_t stream);
+size_t maua_nca_bwd_workspace_bytes(int n, int chn, int hidden, int h, int w);
+int maua_nca_step_bwd(const float* x, const float* g, float* dx, const float* params, int n, int chn, int hidden, int h, int w,
+                      float rate, const float* rate_map, const float* mask, uint64_t seed, int64_t step, int first, void* workspace,
+                      size_t workspace_bytes, maua_stream_t stream);
+int maua_nca_grad_finish(float* grad, int n, int chn, int hidden, int h, int w, const void* workspace, size_t workspace_bytes,
+                         int normalize, maua_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

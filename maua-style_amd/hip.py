@@ -19,6 +19,7 @@ c_i = ctypes.c_int
 c_i64 = ctypes.c_int64
 c_p = ctypes.c_void_p
 c_sz = ctypes.c_size_t
+c_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); mirrors include/maua_hip.h one to one
 SIGNATURES = {
@@ -140,6 +141,12 @@ SIGNATURES = {
     "maua_flow_consistency": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_sz, c_p]),
     "maua_flow_tvl1_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "maua_flow_tvl1": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_nca_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "maua_nca_param_count": (c_i64, [c_i, c_i]),
+    "maua_nca_step": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_u64, c_i64, c_p]),
+    "maua_nca_bwd_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "maua_nca_step_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_u64, c_i64, c_i, c_p, c_sz, c_p]),
+    "maua_nca_grad_finish": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_i, c_p]),
 }
 
 
@@ -1209,4 +1216,82 @@ def flow_tvl1(rgb1, rgb2, levels, warps, iters, block_k, out=None, workspace=Non
         out = torch.empty(2, h, w, dtype=torch.float32, device=rgb1.device)
     _check(lib().maua_flow_tvl1(_u8(rgb1, "rgb1", (h, w, 3)), _u8(rgb2, "rgb2", (h, w, 3)), _ptr(_f32(out, "out")), h, w, int(levels),
                                 int(warps), int(iters), int(block_k), workspace.data_ptr(), workspace.numel(), _stream()), "maua_flow_tvl1")
+    return out
+
+
+# ------------------------------------------------------------------------------------------
+# neural cellular automaton (csrc/nca.hip): state (n, chn, h, w) fp32, params flat [w1][b1][w2]
+# ------------------------------------------------------------------------------------------
+def nca_supported(n, chn, hidden, h, w):
+    return bool(lib().maua_nca_supported(int(n), int(chn), int(hidden), int(h), int(w)))
+
+
+def nca_param_count(chn, hidden):
+    return int(lib().maua_nca_param_count(int(chn), int(hidden)))
+
+
+def _nca_mask_args(x, rate_map, mask):
+    n, _, h, w = x.shape
+    if rate_map is not None and tuple(rate_map.shape) != (h, w):
+        raise HipError(f"nca: rate_map shape {tuple(rate_map.shape)}, expected {(h, w)}")
+    if mask is not None and tuple(mask.shape) not in ((n, h, w), (n, 1, h, w)):
+        raise HipError(f"nca: mask shape {tuple(mask.shape)}, expected {(n, 1, h, w)}")
+    return _ptr(_f32(rate_map, "rate_map")), _ptr(_f32(mask, "mask"))
+
+
+def _nca_mask(mask):
+    """Explicit masks may come as uint8 / bool; the kernel reads fp32."""
+    return mask.float() if mask is not None and mask.dtype in (torch.uint8, torch.bool) else mask
+
+
+def _nca_shape(x, params, chn, hidden):
+    n, c, h, w = x.shape
+    if c != chn:
+        raise HipError(f"nca: state has {c} channels, the model {chn}")
+    if params.numel() != nca_param_count(chn, hidden) or not nca_supported(n, chn, hidden, h, w):
+        raise HipError(f"nca: unsupported chn/hidden {chn}/{hidden} for a {tuple(x.shape)} state")
+    return n, h, w
+
+
+def nca_step(x, params, chn, hidden, rate=0.5, rate_map=None, mask=None, seed=0, step=0, out=None):
+    """One CA step: out = x + mask * W2 relu(W1 perception(x) + b1).  mask: explicit fp32 / uint8 (n, [1,] h, w), or None for the
+    in-kernel mask floor(u(seed, step, b, y, x) + rate) with rate = rate_map[y][x] when given."""
+    n, h, w = _nca_shape(x, params, chn, hidden)
+    if out is None:
+        out = torch.empty_like(x)
+    mask = _nca_mask(mask)
+    rp, mp = _nca_mask_args(x, rate_map, mask)
+    _check(lib().maua_nca_step(_ptr(_f32(x, "x")), _ptr(_f32(out, "out")), _ptr(_f32(params, "params")), n, chn, hidden, h, w,
+                               float(rate), rp, mp, int(seed) & (2 ** 64 - 1), int(step), _stream()), "maua_nca_step")
+    return out
+
+
+def nca_bwd_workspace(n, chn, hidden, h, w, device):
+    need = lib().maua_nca_bwd_workspace_bytes(int(n), int(chn), int(hidden), int(h), int(w))
+    if need == 0:
+        raise HipError(f"nca: unsupported backward shape n={n} chn={chn} hidden={hidden} {h}x{w}")
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def nca_step_bwd(x, g, params, chn, hidden, workspace, first, rate=0.5, rate_map=None, mask=None, seed=0, step=0, dx=None):
+    """Backward of nca_step(x, ...) for the incoming gradient g: returns dx (may be g itself) and adds this step's parameter gradient
+    to the partial slots in `workspace` (first=True clears them)."""
+    n, h, w = _nca_shape(x, params, chn, hidden)
+    if dx is None:
+        dx = torch.empty_like(x)
+    mask = _nca_mask(mask)
+    rp, mp = _nca_mask_args(x, rate_map, mask)
+    _check(lib().maua_nca_step_bwd(_ptr(_f32(x, "x")), _ptr(_f32(g, "g")), _ptr(_f32(dx, "dx")), _ptr(_f32(params, "params")), n, chn,
+                                   hidden, h, w, float(rate), rp, mp, int(seed) & (2 ** 64 - 1), int(step), int(bool(first)),
+                                   workspace.data_ptr(), workspace.numel(), _stream()), "maua_nca_step_bwd")
+    return dx
+
+
+def nca_grad_finish(shape, chn, hidden, workspace, normalize=False, out=None):
+    """The parameter gradient (flat, params layout) summed from the partial slots; normalize: each tensor / (its norm + 1e-8)."""
+    n, _, h, w = shape
+    if out is None:
+        out = torch.empty(nca_param_count(chn, hidden), dtype=torch.float32, device=workspace.device)
+    _check(lib().maua_nca_grad_finish(_ptr(_f32(out, "grad")), n, chn, hidden, h, w, workspace.data_ptr(), workspace.numel(),
+                                      int(bool(normalize)), _stream()), "maua_nca_grad_finish")
     return out
