@@ -210,23 +210,57 @@ class OracleNet:
         self.strength = {i: l.strength for i, l in enumerate(spec) if l.kind in ("content", "style", "tv", "temporal")}
 
     # -- forward ---------------------------------------------------------------------------
-    def _forward(self, x, keep=True):
+    def _forward(self, x, keep=True, decisions=None):
+        """Activations after every spec entry, and the arg-max indices of every max pool.
+
+        `decisions` (B = 1 only; see _check_decisions) pins the network's decisions to someone else's - the engine's, or an
+        oracle's in another precision - and leaves everything else to this oracle's arithmetic: a pinned ReLU passes `h` where
+        its bool mask is set and 0 elsewhere, a pinned max pool gathers `h` at its int64 flat indices (the layout of
+        F.max_pool2d(return_indices=True)).  aux[i] holds the mask of a pinned ReLU and the indices of every max pool."""
+        if decisions is not None:
+            self._check_decisions(x, decisions)
         acts, aux = [], []
         h = x
-        for l in self.spec:
+        for i, l in enumerate(self.spec):
             a = None
             if l.kind == "conv":
                 h = F.conv2d(h, self.w[l.feat_idx], self.b[l.feat_idx], stride=l.stride, padding=l.pad)
             elif l.kind == "relu":
-                h = torch.relu(h)
+                if decisions is None:
+                    h = torch.relu(h)
+                else:
+                    a = decisions[i]
+                    if a.shape != h.shape:
+                        raise ValueError(f"decision of spec entry {i} (relu): shape {tuple(a.shape)}, activation {tuple(h.shape)}")
+                    h = torch.where(a, h, torch.zeros((), dtype=h.dtype))
             elif l.kind == "pool":
                 if l.pool_mode == "max":
-                    h, a = F.max_pool2d(h, l.k, l.stride, 0, ceil_mode=l.ceil, return_indices=True)
+                    if decisions is None:
+                        h, a = F.max_pool2d(h, l.k, l.stride, 0, ceil_mode=l.ceil, return_indices=True)
+                    else:
+                        a = decisions[i]
+                        oh, ow = F.max_pool2d(h[:, :1], l.k, l.stride, 0, ceil_mode=l.ceil).shape[2:]
+                        if a.shape != (*h.shape[:2], oh, ow):
+                            raise ValueError(f"decision of spec entry {i} (max pool): shape {tuple(a.shape)}, pooled {(*h.shape[:2], oh, ow)}")
+                        h = h.reshape(*h.shape[:2], -1).gather(2, a.reshape(*a.shape[:2], -1)).reshape(a.shape)
                 else:
                     h = F.avg_pool2d(h, l.k, l.stride, 0, ceil_mode=l.ceil)
             acts.append(h)
             aux.append(a)
         return acts, aux
+
+    def _check_decisions(self, x, decisions):
+        """A decision for every relu and every max pool and for nothing else; bool masks and int64 indices; one image."""
+        if x.shape[0] != 1:
+            raise NotImplementedError("pinned decisions are for B = 1")
+        want = {i for i, l in enumerate(self.spec) if l.kind == "relu" or (l.kind == "pool" and l.pool_mode == "max")}
+        if set(decisions) != want:
+            raise ValueError(f"decisions for spec entries {sorted(want)}, got {sorted(decisions)}")
+        for i in want:
+            t = decisions[i]
+            dt = torch.bool if self.spec[i].kind == "relu" else torch.int64
+            if not torch.is_tensor(t) or t.dtype != dt or t.device.type != "cpu":
+                raise ValueError(f"decision of spec entry {i} ({self.spec[i].kind}) must be a CPU {dt} tensor")
 
     def _gram_normed(self, f, l):
         # StyleLoss.static_loss: gram / input[idx].nelement()  (loss.py:144)
@@ -299,15 +333,18 @@ class OracleNet:
                 self.strength[i] = self.strength[i] / max(size)
 
     # -- one function evaluation -----------------------------------------------------------
-    def feval(self, x):
+    def feval(self, x, decisions=None):
         """feval closure (optim.py:201-238) for B=1: returns (total, {layer idx: loss}, grad wrt x).
 
         Closed form (SURVEY §8 a-spec).  Reported loss weights vs gradient weights differ when
-        normalize_gradients is on because ScaleGradients is applied to the scalar MSE."""
+        normalize_gradients is on because ScaleGradients is applied to the scalar MSE.
+        `decisions`: ReLU masks and max-pool indices to evaluate under instead of this arithmetic's own (see _forward)."""
         x = x.to(self.dtype)
         if x.shape[0] > 1:
+            if decisions is not None:
+                raise NotImplementedError("pinned decisions are for B = 1")
             return self._feval_window(x)
-        acts, aux = self._forward(x)
+        acts, aux = self._forward(x, decisions=decisions)
         losses, inject = {}, {}
         for i, l in enumerate(self.spec):
             s = self.strength.get(i, 0.0)
@@ -368,12 +405,14 @@ class OracleNet:
                 if l.use_covariance:
                     gf = gf - gf.mean(1).unsqueeze(1)  # backward of the row-mean subtraction
                 inject[i] = gf.reshape(f.shape)
-        g = self._backward(x, acts, aux, inject)
+        g = self._backward(x, acts, aux, inject, decisions=decisions)
         total = sum(losses.values())
         return total, losses, g
 
-    def _backward(self, x, acts, aux, inject):
-        """Backward to the pixels: the injected loss gradients flow down through relu / conv / pool."""
+    def _backward(self, x, acts, aux, inject, decisions=None):
+        """Backward to the pixels: the injected loss gradients flow down through relu / conv / pool.  With `decisions` a ReLU
+        multiplies by its pinned mask (a pinned element may hold a tiny negative value) and a max pool scatters to the pinned
+        indices (which _forward left in aux)."""
         g = None
         for i in range(len(self.spec) - 1, -1, -1):
             l = self.spec[i]
@@ -383,7 +422,7 @@ class OracleNet:
                 continue
             inp = acts[i - 1] if i > 0 else x
             if l.kind == "relu":
-                g = g * (acts[i] > 0).to(g.dtype)
+                g = g * ((acts[i] > 0) if decisions is None else decisions[i]).to(g.dtype)
             elif l.kind == "conv":
                 g = torch.nn.grad.conv2d_input(inp.shape, self.w[l.feat_idx], g, stride=l.stride, padding=l.pad)
             elif l.kind == "pool":

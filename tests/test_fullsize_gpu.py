@@ -262,7 +262,7 @@ def test_full_size_forward_pass_activations_against_fp64(setup, layer, family, p
     import torch.nn.functional as F
     _, _, _, eng, x = setup
     rec, _, step = _routes_by_layer(eng, x)[layer]
-    # (conv5_1 - 512 channels on a 64 x 64 plane, 64 tiles - splits its channel loop four ways; the last arriver of a tile finishes it in the launch)
+    # (conv5_1 - 512 channels on a 64 x 64 plane, 64 tiles - splits its channel loop four ways; the slabs are added by a separate finishing pass)
     assert rec["kernel"] == family and bool(rec.get("pool")) == pooled and rec["ksplit"] == (4 if layer == "conv5_1" else 1), rec
     eng.feval(x)
     torch.cuda.synchronize()
@@ -676,10 +676,14 @@ def test_full_size_evaluation_against_the_oracle(weight_files, model, S):
     the yardstick of test_engine_gpu.py::test_pixel_gradient_is_as_close_to_fp64_as_the_reference_fp32, here at 50 M activations where
     both arithmetics take a few ReLU / arg-max decisions differently from fp64).  NIN: its overlapping 3 x 3 / 2 max pools put so many
     windows within rounding of a tie that decisions, not arithmetic, set both distances - first run 1.86e-3 for the engine, 1.20e-3 for the
-    fp32 oracle, a hundred times the arithmetic's own 1e-5 - and their ratio is luck: 2 x there."""
+    fp32 oracle, a hundred times the arithmetic's own 1e-5 - and their ratio is luck: 2 x there.  So the same comparison runs again with
+    both oracles pinned to the engine's ReLU masks and arg-maxes (tests/engine_decisions.py): what is left is arithmetic, held to 1.5 x the
+    pinned fp32 oracle's distance and 1e-4; and the engine may not take more decisions differently from fp64 than the fp32 oracle does
+    (FLIP_FACTOR x + FLIP_SLACK)."""
     import models
     import optim
     from conftest import make_cfg, NIN_LAYERS
+    from engine_decisions import FLIP_FACTOR, FLIP_SLACK, count_flips, engine_decisions, oracle_decisions
     from oracle import OracleNet, build_spec
     from oracle.style_oracle import loss_order
     extra = ["--style_layers", NIN_LAYERS["style_layers"], "--content_layers", NIN_LAYERS["content_layers"], "--use_covariance"] if model == "nin" else []
@@ -695,20 +699,30 @@ def test_full_size_evaluation_against_the_oracle(weight_files, model, S):
     slots, total, grad = opt.feval()
     torch.cuda.synchronize()
     slots, total, grad = slots.clone().cpu().tolist(), float(total), grad.clone().cpu()
-    del opt
     cfg = make_cfg(**(dict(NIN_LAYERS, use_covariance=True) if model == "nin" else {}))
     sd = synth.nin_state_dict() if model == "nin" else synth.vgg19_state_dict()
-    res = {}
+    res, pinned, nets = {}, {}, {}
     threads = torch.get_num_threads()
     torch.set_num_threads(min(16, threads))   # (the fastest count on many-core hosts: bench.py's thread sweep)
     for dt in (torch.float64, torch.float32):
         onet = OracleNet(build_spec(cfg), sd, dtype=dt)
         onet.capture_content(content)
         onet.capture_style([style], [1.0])
-        res[dt] = onet.feval(init)
-        order = loss_order(onet.spec)
-        names = [onet.spec[i].name for i in order]
-        del onet
+        nets[dt] = onet
+    spec = nets[torch.float64].spec
+    order = loss_order(spec)
+    names = [spec[i].name for i in order]
+    # the engine's ReLU masks and arg-maxes (tests/engine_decisions.py), and the fp32 oracle's, each counted against fp64's
+    acts, aux = nets[torch.float64]._forward(init.double())
+    decisions, e_flips = engine_decisions(opt.engine, spec, acts, aux)
+    del opt
+    acts32, aux32 = nets[torch.float32]._forward(init.float())
+    o_flips = count_flips(spec, oracle_decisions(spec, acts32, aux32), acts, aux)
+    del acts, aux, acts32, aux32
+    for dt in (torch.float64, torch.float32):
+        res[dt] = nets[dt].feval(init)
+        pinned[dt] = nets[dt].feval(init, decisions=decisions)[2]
+    del nets
     torch.set_num_threads(threads)
     t64, l64, g64 = res[torch.float64]
     assert len(order) == len(slots)
@@ -717,11 +731,17 @@ def test_full_size_evaluation_against_the_oracle(weight_files, model, S):
         assert abs(slots[k] - want) <= 1e-4 * max(abs(want), 1e-9), (names[k], slots[k], want)
     assert abs(total - float(t64)) <= 1e-4 * abs(float(t64))
     ours, theirs = rel_l2(grad, g64), rel_l2(res[torch.float32][2], g64)
-    print(f"{model} {S}: pixel gradient against the fp64 oracle: engine {ours:.3e}, fp32 oracle {theirs:.3e}")
+    ours_pinned, theirs_pinned = rel_l2(grad, pinned[torch.float64]), rel_l2(pinned[torch.float32], pinned[torch.float64])
+    e, o = sum(e_flips.values()), sum(o_flips.values())
+    print(f"{model} {S}: pixel gradient against the fp64 oracle: engine {ours:.3e}, fp32 oracle {theirs:.3e}; pinned to the engine's decisions: "
+          f"engine {ours_pinned:.3e}, fp32 oracle {theirs_pinned:.3e}; decisions off fp64: engine {e}, fp32 oracle {o}")
     # (both distances are set by the handful of decisions each arithmetic takes differently from fp64, and the fp32 oracle's depend on how
     #  the host's BLAS threads split its sums: the ratio is held where it was measured, the absolute level is the fallback on another host)
     assert ours <= max((2.0 if model == "nin" else 1.5) * theirs, 4e-3 if model == "nin" else 3e-3), (ours, theirs)   # (measured: VGG-19 1.37e-3 / 1.18e-3, NIN 1.86e-3 / 1.20e-3)
     assert theirs <= 1e-2    # (the yardstick itself is sane)
+    # ... and with every decision pinned to the engine's, what is left is arithmetic: as close to fp64 as fp32 is, and never above 1e-4
+    assert ours_pinned <= min(1.5 * theirs_pinned, 1e-4), (ours_pinned, theirs_pinned)
+    assert e <= FLIP_FACTOR * o + FLIP_SLACK, (e, o, {spec[i].name or i: n for i, n in e_flips.items() if n})
 
 
 def test_full_length_lbfgs_against_the_oracle():

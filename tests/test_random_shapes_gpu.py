@@ -174,11 +174,11 @@ def test_random_geometry_of_the_pooling_and_unpooling_forms(hip, seed):
     assert rel_l2(gx.cpu(), refb) <= BAR or float((gx.cpu().double() - refb).abs().max()) <= 1e-6 * float(refb.abs().max() or 1.0), (family, cin, cout, H, W, n, honour, masked)
 
 
-def draw_config(seed):
+def draw_config(seed, scale=None):
     r = random.Random(9000 + seed + BASE)
     nin = seed >= 32   # (the last sixteen configurations: the alternative backbone, reference models.py:74-113)
     S = r.randint(150, 420) if nin else r.randint(40, 200)   # (NIN's stem divides the image by four; three ceil-mode pools follow)
-    S = int(S * SCALE)
+    S = int(S * (SCALE if scale is None else scale))
     relus = [f"relu{i}" for i in range(1, 13)] if nin else \
         ["relu1_1", "relu1_2", "relu2_1", "relu2_2", "relu3_1", "relu3_2", "relu3_3", "relu3_4", "relu4_1", "relu4_2", "relu4_3", "relu4_4", "relu5_1"]
     style = sorted(r.sample(relus, r.randint(1, 5)), key=relus.index)
@@ -209,15 +209,34 @@ def test_random_configurations_against_the_cpu_oracle(weight_files, seed):
     fixtures): image sides 40 ... 200 (odd planes and floor-mode pools included), one to five style layers and one or two content layers
     anywhere between relu1_1 and relu5_1 (fused and unfused Gram backward, content losses on and off the fused-pool groups, networks cut at
     any depth), max / avg pooling, --no_grad_norm, --normalize_weights, --use_covariance, two style images with blend weights, TV on and
-    off.  The goldens cover twelve configurations the reference was run on; this covers what nobody listed.  Bars: every module's loss
-    1e-4, pixel gradient 1e-4 rel-L2 (the bars of test_engine_feval_matches_reference)."""
+    off.  The goldens cover twelve configurations the reference was run on; this covers what nobody listed.  Bars: see
+    _check_random_configuration."""
+    _check_random_configuration(weight_files, seed, None)
+
+
+@pytest.mark.parametrize("seed", range(0, 48, 6))
+def test_random_configurations_at_three_times_the_size(weight_files, seed):
+    """The same at three times the image side (VGG-19 120 ... 600 pixels, NIN 450 ... 1260): the sizes where the wide kernels
+    (conv_x3p / conv_x3q), the pooling epilogues and unpooling prologues and the fused Gram backward are routed, under the same bars."""
+    _check_random_configuration(weight_files, seed, 3 * SCALE)
+
+
+def _check_random_configuration(weight_files, seed, scale):
+    """Bars: every module's loss 1e-4 of the fp64 oracle (the bar of test_engine_feval_matches_reference).  The engine's decisions - ReLU
+    masks, max-pool arg-maxes (tests/engine_decisions.py) - pin a second fp64 evaluation, which then differs from the engine by arithmetic
+    alone: every materialised activation 2e-6 of the pinned forward, the pixel gradient 1e-4 rel-L2 of the pinned gradient, whatever the
+    decisions.  Unpinned, a decision within rounding of its boundary can fall on the other side than in fp64 (at
+    S = 151 with avg pooling ONE relu2_1 activation of 720 000 is 0 here and 2.7e-5 in fp64 and moves the image gradient by 1.6e-3): the
+    unpinned gradient is held to 1e-4 when the engine takes every decision as fp64 does, and the number of decisions it takes otherwise
+    is bounded by the fp32 oracle's on the same inputs."""
     import models
     import optim
     import synth
     from conftest import product_args
+    from engine_decisions import FLIP_FACTOR, FLIP_SLACK, activation_map, count_flips, engine_decisions, oracle_decisions
     from oracle import OracleNet, build_spec
     from oracle.style_oracle import loss_order
-    S, extra, two_styles, nin = draw_config(seed)
+    S, extra, two_styles, nin = draw_config(seed, scale)
     styles = ("s.png", "t.png") if two_styles else ("s.png",)
     args = product_args(weight_files, extra, model="nin" if nin else "vgg19", S=S, N=3, styles=styles)
     content, style, init = synth.images(S)
@@ -235,75 +254,53 @@ def test_random_configurations_against_the_cpu_oracle(weight_files, seed):
     slots, total, grad = opt.feval()
     torch.cuda.synchronize()
     slots, grad = slots.clone().cpu(), grad.clone().cpu()
+    assert opt.engine is not None, (seed, S, extra, "evaluated off the fused engine: no decisions to read")
     sd = synth.nin_state_dict() if nin else synth.vgg19_state_dict()
-    onet = OracleNet(build_spec(args), sd, dtype=torch.float64)
-    onet.capture_content(content)
-    onet.capture_style(style_images, args.style_blend_weights)
-    if args.normalize_weights:
-        onet.normalize_weights()
-    ototal, olosses, ograd = onet.feval(init)
-    order = loss_order(onet.spec)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(min(16, os.cpu_count() or 1))   # (fp64 and the decision counts do not depend on it)
+    try:
+        nets = {}
+        for dt in (torch.float64, torch.float32):
+            onet = OracleNet(build_spec(args), sd, dtype=dt)
+            onet.capture_content(content)
+            onet.capture_style(style_images, args.style_blend_weights)
+            if args.normalize_weights:
+                onet.normalize_weights()
+            nets[dt] = onet
+        onet = nets[torch.float64]
+        spec = onet.spec
+        ototal, olosses, ograd = onet.feval(init)
+        acts, aux = onet._forward(init.double())
+        decisions, e_flips = engine_decisions(opt.engine, spec, acts, aux)
+        acts32, aux32 = nets[torch.float32]._forward(init.float())
+        o_flips = count_flips(spec, oracle_decisions(spec, acts32, aux32), acts, aux)
+        del acts32, aux32
+        pacts, _ = onet._forward(init.double(), decisions=decisions)
+        _, _, pgrad = onet.feval(init, decisions=decisions)
+    finally:
+        torch.set_num_threads(threads)
+    order = loss_order(spec)
     got = slots.tolist()
     for k, i in enumerate(order):
         want = float(olosses.get(i, 0.0))
-        assert abs(got[k] - want) <= 1e-4 * max(abs(want), 1e-9), (seed, S, extra, onet.spec[i].name, got[k], want)
-    diff = grad.double() - ograd.double()
-    rel = float(diff.norm() / ograd.double().norm())
-    # A ReLU decision within rounding of its boundary can fall on the other side than in fp64 ("decision-bound calls":
-    # at S = 151 with avg pooling ONE relu2_1 activation of 720 000 is 0 here and 2.7e-5 - of typically 60 - in fp64, and its gradient of
-    # typical size then moves the image gradient by 1.6e-3 rel-L2, all of it inside the activation's receptive field).  Such a flip is not
-    # an error of the arithmetic: up to three 40 x 40 windows around the largest differences are set aside, the rest must meet the bar.
-    flips = 0
-    if rel > 1e-4 and opt.engine is not None:
-        # ... and such flips can be SEEN: the engine's saved activations against the oracle's (they agree to 1e-7 .. 4e-7 everywhere; an
-        # element that is positive on one side only is a flipped decision).  A deep flip's receptive field is a tenth of the image (NIN,
-        # 322 px: two flips, image gradient 1.5e-3 off with 79 % of the squared error in 1 % of the pixels): no window rule holds
-        # there, so with flips in sight the bar is a sanity bound and the strict one applies to what decisions cannot explain.
-        acts, _ = onet._forward(init.double())
-        for k, v in opt.engine.act.items():
-            if k == 0 or v is None or v.is_meta:
-                continue
-            ev = v.cpu().double()
-            cands = [oa for oa in acts if tuple(oa.shape) == tuple(ev.shape)]
-            oa = min(cands, key=lambda t: float((ev - t).norm()))
-            assert float((ev - oa).norm() / oa.norm()) <= 2e-6, (seed, k)
-            flips += int(((ev > 0) ^ (oa > 0)).sum())
-        # ... and so can the other kind of decision, the arg-max of a max-pooling window whose two largest entries lie within rounding of
-        # each other (found by the fuzzing campaign of round 6, RANDOM_SHAPES_BASE = 1 ... 6: six of 288 configurations, five of them NIN
-        # with its overlapping 3 x 3 windows, 1.6e-4 ... 9.2e-4 off with every activation equal to 1e-7): the engine's decision - from the
-        # activation it pooled, or from the decision bytes where the convolution's epilogue pooled - against the oracle's indices, counted
-        # where the window's maximum is positive (a maximum of zero passes no gradient).
-        acts, aux = onet._forward(init.double())
-        epools = [st for st in opt.engine.steps if st.kind == "pool"]
-        opools = [i for i, l in enumerate(onet.spec) if l.kind == "pool"]
-        assert len(epools) == len(opools)
-        for st, i in zip(epools, opools):
-            l = onet.spec[i]
-            if l.pool_mode != "max":
-                continue
-            src = opt.engine.act[st.src]
-            if not src.is_meta:
-                eidx = F.max_pool2d(src.cpu(), l.k, l.stride, 0, ceil_mode=l.ceil, return_indices=True)[1]
-            else:   # fused into the producing launch: byte = corner (2 dy + dx) | 4 where the maximum is not positive
-                from conftest import planar_codes
-                codes = planar_codes(opt.engine.pool_codes[id(st)].cpu()).long()   # ([image][c / 8][pooled pixel][c % 8] in memory)
-                hp, wp = codes.shape[2:]
-                w_in = acts[i - 1].shape[3]
-                py = torch.arange(hp).view(1, 1, hp, 1)
-                px = torch.arange(wp).view(1, 1, 1, wp)
-                eidx = (2 * py + ((codes & 3) >> 1)) * w_in + 2 * px + (codes & 1)
-            flips += int(((eidx != aux[i]) & (acts[i] > 0)).sum())
-    if flips:
-        assert rel <= 2e-2 * flips, (seed, S, extra, rel, flips)
-        return
-    windows = 0
-    while rel > 1e-4 and windows < 3:
-        amp = diff.abs().sum(dim=(0, 1))
-        y, x = divmod(int(amp.argmax()), amp.shape[1])
-        diff[:, :, max(0, y - 20):y + 20, max(0, x - 20):x + 20] = 0
-        rel = float(diff.norm() / ograd.double().norm())
-        windows += 1
-    assert rel <= 1e-4, (seed, S, extra, rel, windows, opt.engine is not None)
+        assert abs(got[k] - want) <= 1e-4 * max(abs(want), 1e-9), (seed, S, extra, spec[i].name, got[k], want)
+    checked = 0
+    for k, i in activation_map(opt.engine, spec).items():
+        v = opt.engine.act[k]
+        if v.is_meta:
+            continue   # (pooled in the producing launch: only the pooled map exists)
+        err = rel_l2(v.cpu(), pacts[i])
+        assert err <= 2e-6, (seed, S, extra, k, spec[i].kind, err)
+        checked += 1
+    assert checked > 0
+    rel, pinned = rel_l2(grad, ograd), rel_l2(grad, pgrad)
+    e, o = sum(e_flips.values()), sum(o_flips.values())
+    print(f"random configuration {seed} (S = {S}, {'nin' if nin else 'vgg19'}): gradient {rel:.2e} unpinned, {pinned:.2e} pinned; "
+          f"decisions off fp64: engine {e}, fp32 oracle {o}")
+    assert pinned <= 1e-4, (seed, S, extra, pinned, rel, e)
+    assert e <= FLIP_FACTOR * o + FLIP_SLACK, (seed, S, extra, e, o, {spec[i].name or i: n for i, n in e_flips.items() if n})
+    if e == 0:
+        assert rel <= 1e-4, (seed, S, extra, rel)
 
 
 @pytest.mark.parametrize("seed", range(20))

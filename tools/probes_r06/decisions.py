@@ -7,12 +7,12 @@ import sys
 import tempfile
 
 import torch
-import torch.nn.functional as F
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [REPO, os.path.join(REPO, "maua-style_amd"), os.path.join(REPO, "tests")]
 import synth  # noqa: E402
-from conftest import planar_codes, product_args  # noqa: E402
+from conftest import product_args  # noqa: E402
+from engine_decisions import activation_map, count_flips, engine_decisions, oracle_decisions  # noqa: E402
 import test_random_shapes_gpu as T  # noqa: E402
 from oracle import OracleNet, build_spec  # noqa: E402
 import models  # noqa: E402
@@ -57,37 +57,17 @@ for seed in [int(a) for a in sys.argv[1:]]:
     g32, a32, x32, _ = out[torch.float32]
     rel = float((grad.double() - g64).norm() / g64.norm())
     theirs = float((g32.double() - g64).norm() / g64.norm())
-    # decisions of the fp32 oracle against the fp64 oracle
-    o_relu = sum(int(((a > 0) ^ (b > 0)).sum()) for a, b, l in zip(a32, a64, spec) if l.kind == "relu")
-    o_pool = sum(int(((i32 != i64) & (b > 0)).sum()) for i32, i64, b, l in zip(x32, x64, a64, spec) if l.kind == "pool" and i64 is not None)
-    # decisions of the engine against the fp64 oracle
-    e_relu = 0
-    worst = 0.0
-    for k, v in opt.engine.act.items():
-        if k == 0 or v is None or v.is_meta:
-            continue
-        ev = v.cpu().double()
-        cands = [oa for oa in a64 if tuple(oa.shape) == tuple(ev.shape)]
-        oa = min(cands, key=lambda t: float((ev - t).norm()))
-        worst = max(worst, float((ev - oa).norm() / oa.norm()))
-        e_relu += int(((ev > 0) ^ (oa > 0)).sum())
-    e_pool = 0
-    epools = [st for st in opt.engine.steps if st.kind == "pool"]
-    opools = [i for i, l in enumerate(spec) if l.kind == "pool"]
-    for st, i in zip(epools, opools):
-        l = spec[i]
-        if l.pool_mode != "max":
-            continue
-        src = opt.engine.act[st.src]
-        if not src.is_meta:
-            eidx = F.max_pool2d(src.cpu(), l.k, l.stride, 0, ceil_mode=l.ceil, return_indices=True)[1]
-        else:
-            codes = planar_codes(opt.engine.pool_codes[id(st)].cpu()).long()
-            hp, wp = codes.shape[2:]
-            w_in = a64[i - 1].shape[3]
-            eidx = (2 * torch.arange(hp).view(1, 1, hp, 1) + ((codes & 3) >> 1)) * w_in + 2 * torch.arange(wp).view(1, 1, 1, wp) + (codes & 1)
-        e_pool += int(((eidx != x64[i]) & (a64[i] > 0)).sum())
-    print(f"seed {seed} S={S} {'nin' if nin else 'vgg19'}: engine vs fp64 {rel:.2e} (ReLU flips {e_relu}, arg-max flips {e_pool}, worst activation {worst:.1e});  "
+    # decisions of the fp32 oracle and of the engine (tests/engine_decisions.py) against the fp64 oracle's
+    o_flips = count_flips(spec, oracle_decisions(spec, a32, x32), a64, x64)
+    decisions, e_flips = engine_decisions(opt.engine, spec, a64, x64)
+    o_relu = sum(n for i, n in o_flips.items() if spec[i].kind == "relu")
+    o_pool = sum(n for i, n in o_flips.items() if spec[i].kind == "pool")
+    e_relu = sum(n for i, n in e_flips.items() if spec[i].kind == "relu")
+    e_pool = sum(n for i, n in e_flips.items() if spec[i].kind == "pool")
+    pacts, _ = OracleNet(spec, sd, dtype=torch.float64)._forward(init.double(), decisions=decisions)
+    worst = max((float((opt.engine.act[k].cpu().double() - pacts[i]).norm() / pacts[i].norm())
+                 for k, i in activation_map(opt.engine, spec).items() if not opt.engine.act[k].is_meta), default=0.0)
+    print(f"seed {seed} S={S} {'nin' if nin else 'vgg19'}: engine vs fp64 {rel:.2e} (ReLU flips {e_relu}, arg-max flips {e_pool}, worst activation against the pinned forward {worst:.1e});  "
           f"fp32 oracle vs fp64 {theirs:.2e} (ReLU flips {o_relu}, arg-max flips {o_pool})   {' '.join(extra)}", flush=True)
     del opt, net, losses
     torch.cuda.empty_cache()
