@@ -65,6 +65,83 @@ def test_backward_matches_central_differences(steps):
         assert abs(fd - dp[i]) <= 1e-6 * max(1.0, abs(fd)), (i, fd, dp[i])
 
 
+# ---- what the element-wise backward comparison of tests/test_nca_bwd_gpu.py stands on ---------------------------------------------
+def _preact(x, params, chn, hidden):
+    w1, b1, _ = R.split(params, chn, hidden, x.dtype)
+    return np.einsum("jk,bkhw->bjhw", w1, R.perceive(x)) + b1[None, :, None, None]
+
+
+@pytest.mark.parametrize("chn,hidden", R.PAIRS)
+def test_zeroed_gradient_makes_the_backward_independent_of_near_tie_decisions(chn, hidden):
+    """With g = 0 on the near_tie pixels, flipping every hidden unit's ReLU decision at every flagged pixel changes no output."""
+    n, h, w = 2, 19, 23
+    params = R.case_params(chn, hidden, 1)
+    x, g = (a.astype(np.float64) for a in R.case_state(chn, n, h, w))
+    m, _ = R.case_mask(n, h, w, "ones")
+    tie = R.near_tie(x, params, chn, hidden)
+    assert tie.any() and tie.mean() <= R.TIE_SHARE
+    flipped = (_preact(x, params, chn, hidden) > 0) ^ tie[:, None]
+    g0 = g * ~tie[:, None]
+    want = R.step_bwd(x, g0, params, chn, hidden, m)
+    got = R.step_bwd(x, g0, params, chn, hidden, m, relu=flipped)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b)
+    for a, b in zip(R.step_bwd_abs(x, g0, params, chn, hidden, m, relu=flipped), R.step_bwd_abs(x, g0, params, chn, hidden, m)):
+        assert np.array_equal(a, b)
+    # and the zeroing is what does it: with g left alone the flipped decisions move dx
+    assert not np.array_equal(R.step_bwd(x, g, params, chn, hidden, m, relu=flipped)[0], R.step_bwd(x, g, params, chn, hidden, m)[0])
+
+
+def test_near_tie_share_of_every_backward_case():
+    """The condition of the element-wise GPU cases: at most 2 % of the pixels lose their gradient, for every (pair, shape)."""
+    cases = R.bwd_cases()
+    assert {c[2:5] for c in cases} >= {R.SLOT_SHAPE, R.CHAIN_SHAPE, R.EXTREME_SHAPE} | set(R.MASK_SHAPES) | set(R.PLAN_SHAPES)
+    seen = {}
+    for chn, hidden, n, h, w, _ in cases:
+        if (chn, n, h, w) not in seen:
+            x = R.case_state(chn, n, h, w)[0].astype(np.float64)
+            seen[chn, n, h, w] = float(R.near_tie(x, R.case_params(chn, hidden, 1), chn, hidden).mean())
+    assert max(seen.values()) <= R.TIE_SHARE, {k: v for k, v in seen.items() if v > R.TIE_SHARE}
+    assert seen[12, 4, 160, 160] > 0 and seen[16, 3, 150, 170] > 0  # (the flagged set is not empty where it matters)
+
+
+@pytest.mark.parametrize("chn,hidden,n,h,w,mode", [(12, 96, 2, 19, 23, "rate0.5"), (16, 128, 1, 5, 13, "ones"), (12, 96, 3, 2, 1, "given"),
+                                                   (16, 128, 1, 1, 1, "ones")])
+def test_abs_backward_bounds_the_backward(chn, hidden, n, h, w, mode):
+    params = R.case_params(chn, hidden, 1)
+    x, g = (a.astype(np.float64) for a in R.case_state(chn, n, h, w))
+    m, _ = R.case_mask(n, h, w, mode)
+    for v, a in zip(R.step_bwd(x, g, params, chn, hidden, m), R.step_bwd_abs(x, g, params, chn, hidden, m)):
+        assert v.shape == a.shape and np.all(a >= 0) and np.all(np.abs(v) <= a * (1 + 1e-12))
+
+
+@pytest.mark.parametrize("chn,hidden", R.PAIRS)
+def test_near_tie_scale_dominates_the_fp32_error_of_the_preactivation(chn, hidden):
+    """|a32 - a64| <= 5e-6 S everywhere (the derivation in near_tie's docstring gives 4.1e-6 S for any evaluation order): half of
+    near_tie's tolerance, so an fp32 decision outside the flagged set is the fp64 decision."""
+    params = R.case_params(chn, hidden, 1)
+    x = R.case_state(chn, 3, 150, 170)[0]
+    a32 = _preact(x, params, chn, hidden)
+    assert a32.dtype == np.float32
+    a64 = _preact(x.astype(np.float64), params, chn, hidden)
+    S = R.preact_scale(x.astype(np.float64), params, chn, hidden)[1]
+    assert np.all(np.abs(a32 - a64) <= 5e-6 * S), float(np.max(np.abs(a32 - a64) / S))
+    tie = R.near_tie(x.astype(np.float64), params, chn, hidden)
+    assert np.array_equal((a32 > 0)[~np.broadcast_to(tie[:, None], a32.shape)], (a64 > 0)[~np.broadcast_to(tie[:, None], a32.shape)])
+
+
+def test_restatement_follows_the_dtype_of_the_state():
+    """The fp32 twin of the folded-chain test: the same functions on fp32 arrays stay in fp32 and land near the fp64 result."""
+    chn, hidden, n, h, w = 12, 96, 2, 9, 11
+    params = R.case_params(chn, hidden, 4, w2_scale=0.01, w1_scale=0.03)
+    x, g = R.case_state(chn, n, h, w)
+    masks = [R.mask(5, k, n, h, w) for k in range(3)]
+    d32, p32 = R.chain_bwd(x, g, params, chn, hidden, masks)
+    d64, p64 = R.chain_bwd(x.astype(np.float64), g.astype(np.float64), params, chn, hidden, masks)
+    assert d32.dtype == p32.dtype == np.float32 and d64.dtype == p64.dtype == np.float64
+    assert 0 < np.linalg.norm(d32 - d64) <= 1e-5 * np.linalg.norm(d64) and 0 < np.linalg.norm(p32 - p64) <= 1e-4 * np.linalg.norm(p64)
+
+
 def _splitmix_scalar(z):
     z = (z + 0x9E3779B97F4A7C15) & R.M64
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & R.M64
