@@ -444,6 +444,27 @@ int maua_resize_bilinear(const float* x, float* y, int planes, int h, int w, int
 int maua_deprocess_u8(const float* x_bgr_chw, unsigned char* out_rgb_hwc, int h, int w, float mean_b, float mean_g, float mean_r,
                       maua_stream_t stream);
 
+/* ---- temporally consistent vid_img on the device (csrc/warp.hip; style._vid_img_flow with the plan field temporal_device = 1) ----
+ * maua_flow_warp_grid: load.flow_warp_map (reference load.py:191-214; called at style.py:252,280) from a flow field already on the
+ *   device, float [h][w][2] in pixels as a .flo file stores it: u / w and v / h (fp32), scipy.ndimage.gaussian_filter(sigma 5: 41 taps,
+ *   weights and sums in fp64, `reflect` boundary repeated for sides shorter than the radius, axis 0 then axis 1, fp32 intermediate),
+ *   + linspace(-1, 1, w) / linspace(-1, 1, h) in fp64, rounded to fp32, then F.interpolate(size=(oh, ow), mode="bilinear",
+ *   align_corners=False) with maua_resize_bilinear's coordinates -> grid float [oh][ow][2] (8-byte aligned).  h, w >= 1.
+ *   workspace: maua_flow_warp_grid_workspace_bytes(h, w) (the smoothed map before the resize).
+ * maua_grid_sample_border: F.grid_sample(x, grid, mode="bilinear", padding_mode="border", align_corners=False) (reference
+ *   style.py:253,281): x (n, c, h, w), grid (n, oh, ow, 2) -> y (n, c, oh, ow); position ((g + 1) * size - 1) / 2 clamped to
+ *   [0, size - 1], four taps at clamped indices; positions and weights in fp64, once per output pixel for all channels.
+ *   blend / init (both or neither; need h x w == oh x ow): init = (1 - blend_a) * blend + blend_a * x, the temporal blend of
+ *   style.py:286, from the same pass over x (fp64 arithmetic, one rounding).
+ * maua_mask_u8_resize: load.reliable_flow_weighting + F.interpolate (reference load.py:217-218, style.py:282): mask bytes [h][w][c]
+ *   (c <= 4) -> float [c][oh][ow] = bilinear resize (maua_resize_bilinear's arithmetic) of byte / 255. */
+size_t maua_flow_warp_grid_workspace_bytes(int h, int w);
+int maua_flow_warp_grid(const float* flow_hw2, float* grid_hw2, int h, int w, int oh, int ow, void* workspace, size_t workspace_bytes,
+                        maua_stream_t stream);
+int maua_grid_sample_border(const float* x, const float* grid, float* y, int n, int c, int h, int w, int oh, int ow, const float* blend,
+                            double blend_a, float* init, maua_stream_t stream);
+int maua_mask_u8_resize(const uint8_t* mask_hwc, float* out_chw, int h, int w, int c, int oh, int ow, maua_stream_t stream);
+
 /* ---- batches of independent frames (vid_img without optical flow, reference style.py:192-290) ---------- */
 /* The library's tuning constants - routing thresholds and experiment switches (which kernel family a shape gets, forced K splits, the
  * 128 x 128 Gram blocks ...): the host side's planner configuration (maua-style_amd/plan.py lists every name with its default and

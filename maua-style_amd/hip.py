@@ -87,6 +87,10 @@ SIGNATURES = {
     "maua_color_match_apply": (c_i, [c_p, c_p, c_f, c_p, c_p, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     "maua_resize_bilinear": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_p]),
     "maua_deprocess_u8": (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_p]),
+    "maua_flow_warp_grid_workspace_bytes": (c_sz, [c_i, c_i]),
+    "maua_flow_warp_grid": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_grid_sample_border": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, ctypes.c_double, c_p, c_p]),
+    "maua_mask_u8_resize": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_set_tuning": (c_i, [ctypes.c_char_p, ctypes.c_double]),
     "maua_get_tuning": (ctypes.c_double, [ctypes.c_char_p, ctypes.c_double]),
     "maua_set_split_batch_hint": (None, [c_i]),
@@ -1052,6 +1056,59 @@ def deprocess_u8(x, mean_bgr):
     out = torch.empty(h, w, 3, dtype=torch.uint8, device=x.device)
     _check(lib().maua_deprocess_u8(_ptr(_f32(x3, "x")), out.data_ptr(), h, w, float(mean_bgr[0]), float(mean_bgr[1]),
                                    float(mean_bgr[2]), _stream()), "maua_deprocess_u8")
+    return out
+
+
+def flow_warp_grid(flo, size, workspace=None):
+    """load.flow_warp_map from a device flow field (h, w, 2) in pixels, as a .flo file stores it: the (1, H, W, 2) sampling grid of
+    F.grid_sample for size = (H, W)."""
+    if flo.dim() != 3 or flo.shape[2] != 2:
+        raise HipError(f"flow_warp_grid: flow of shape {tuple(flo.shape)}, expected (h, w, 2)")
+    h, w = int(flo.shape[0]), int(flo.shape[1])
+    oh, ow = int(size[0]), int(size[1])
+    if oh <= 0 or ow <= 0:
+        raise HipError(f"flow_warp_grid: output {oh}x{ow}")
+    need = lib().maua_flow_warp_grid_workspace_bytes(h, w)
+    if not need:
+        raise HipError(f"flow_warp_grid: flow field {h}x{w}")
+    grid = torch.empty(1, oh, ow, 2, device=flo.device, dtype=torch.float32)
+    if workspace is None:  # allocated after the result and held until the launches are enqueued: it must not share memory with `grid`
+        workspace = torch.empty(need, dtype=torch.uint8, device=flo.device)
+    _check(lib().maua_flow_warp_grid(_ptr(_f32(flo, "flo")), _ptr(grid), h, w, oh, ow, workspace.data_ptr(),
+                                     workspace.numel() * workspace.element_size(), _stream()), "maua_flow_warp_grid")
+    return grid
+
+
+def grid_sample_border(x, grid, blend=None, blend_a=0.0):
+    """F.grid_sample(x, grid, mode="bilinear", padding_mode="border", align_corners=False) for x (N,C,h,w) and grid (N,H,W,2).
+    With `blend` (shaped like x, h x w == H x W) returns (sampled, (1 - blend_a) * blend + blend_a * x): both from one pass over x."""
+    if x.dim() != 4 or grid.dim() != 4 or grid.shape[0] != x.shape[0] or grid.shape[3] != 2:
+        raise HipError(f"grid_sample_border: x {tuple(x.shape)}, grid {tuple(grid.shape)}")
+    n, c, h, w = (int(v) for v in x.shape)
+    oh, ow = int(grid.shape[1]), int(grid.shape[2])
+    out = torch.empty(n, c, oh, ow, device=x.device, dtype=torch.float32)
+    init = None
+    if blend is not None:
+        if tuple(blend.shape) != tuple(x.shape) or (h, w) != (oh, ow):
+            raise HipError(f"grid_sample_border: blend {tuple(blend.shape)} with x {tuple(x.shape)} sampled to {oh}x{ow}")
+        init = torch.empty_like(out)
+    _check(lib().maua_grid_sample_border(_ptr(_f32(x, "x")), _ptr(_f32(grid, "grid")), _ptr(out), n, c, h, w, oh, ow,
+                                         _ptr(_f32(blend, "blend")), float(blend_a), _ptr(init), _stream()), "maua_grid_sample_border")
+    return out if blend is None else (out, init)
+
+
+def mask_u8_resize(mask, size):
+    """load.reliable_flow_weighting + F.interpolate(size=size, mode="bilinear", align_corners=False): a uint8 device mask (h, w) or
+    (h, w, c) -> (1, c, H, W) float in [0, 1]."""
+    m = mask if mask.dim() == 3 else mask.unsqueeze(-1)
+    if m.dim() != 3:
+        raise HipError(f"mask_u8_resize: mask of shape {tuple(mask.shape)}")
+    h, w, c = (int(v) for v in m.shape)
+    oh, ow = int(size[0]), int(size[1])
+    if oh <= 0 or ow <= 0:
+        raise HipError(f"mask_u8_resize: output {oh}x{ow}")
+    out = torch.empty(1, c, oh, ow, device=m.device, dtype=torch.float32)
+    _check(lib().maua_mask_u8_resize(_u8(m, "mask"), _ptr(out), h, w, c, oh, ow, _stream()), "maua_mask_u8_resize")
     return out
 
 

@@ -42,6 +42,15 @@ def preprocess_u8(rgb_hwc):
     return (bgr - _MEAN_BGR.to(rgb_hwc.device)[:, None, None]).unsqueeze(0)
 
 
+def preprocess_device(image_path):
+    """`preprocess` of a file for a caller that also holds such images as 8-bit device tensors: the PNG is decoded on the host, its bytes
+    are uploaded and go through `preprocess_u8` there - the same device arithmetic on the same bytes, so an image read back from its file
+    and the image kept in memory give the same bits (a device division by 255 is a multiplication by its reciprocal: `preprocess` on the
+    host and `preprocess_u8` on the device differ in the last place)."""
+    img = Image.open(fetch(image_path)).convert("RGB")
+    return preprocess_u8(th.from_numpy(np.asarray(img, dtype=np.uint8).copy()).cuda())
+
+
 def deprocess(output_tensor):
     """(1,3,H,W) network-space tensor -> PIL RGB image; values are clamped to [0,1] and truncated to 8 bits like
     torchvision's ToPILImage (load.py:47-52)."""
@@ -176,6 +185,25 @@ def flow_warp_map(filename, current_size):
     grid = th.from_numpy((np.stack([gx, gy], axis=2) + flow).astype(np.float32)).unsqueeze(0)
     return F.interpolate(grid.permute(0, 3, 1, 2), size=tuple(current_size), mode="bilinear",
                          align_corners=False).permute(0, 2, 3, 1)
+
+
+def flow_warp_grid_device(filename, current_size):
+    """`flow_warp_map` on the device: the field of the .flo file is uploaded as stored and smoothed, offset and resized by
+    csrc/warp.hip.  Returns a (1, H, W, 2) device tensor."""
+    import hip
+    flo = th.from_numpy(read_flo(filename)).cuda()
+    return hip.flow_warp_grid(flo, tuple(int(v) for v in current_size))
+
+
+def reliable_flow_weighting_device(filename, current_size):
+    """`reliable_flow_weighting` + the bilinear resize to `current_size` on the device: the PNG's bytes are uploaded and become the
+    (1, C, H, W) float mask there; a mask that is not 8-bit is converted on the host as before and resized on the device."""
+    import hip
+    arr = np.asarray(Image.open(filename))
+    size = tuple(int(v) for v in current_size)
+    if arr.dtype != np.uint8:
+        return hip.resize_bilinear(reliable_flow_weighting(filename).cuda().contiguous(), size=size)
+    return hip.mask_u8_resize(th.from_numpy(np.array(arr)).cuda(), size)
 
 
 def reliable_flow_weighting(filename):

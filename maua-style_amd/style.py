@@ -178,6 +178,8 @@ def _vid_img_flow(args, output_dir, frames, style_images_big, content_size):
     (`<output_dir>/flow/{forward,backward}_<prev>_<this>.flo` + `.png` reliability masks, as its flow networks leave them;
     `--flow_models tvl1` has flow.write_flow_cache estimate them first).  Frames depend on their predecessor (warped previous
     result = initialisation and pixel-level temporal target), so this path is sequential: one rank runs it."""
+    if plan.on("temporal_device") and th.cuda.is_available():
+        return _vid_img_flow_device(args, output_dir, frames, style_images_big, content_size)
     passes = max(1, args.passes_per_scale)
     prev_size = None
     for size_n, (current_size, num_iters) in enumerate(zip(args.image_sizes, args.num_iters)):
@@ -326,6 +328,157 @@ def _optimize_group(contents, style_images, inits, num_iters, args, net, losses,
     except engine.UnsupportedNet:
         return th.cat([optim.optimize(c, style_images, p, num_iters, args, net, losses, keep_on_device=True)
                        for c, p in zip(contents, inits)])
+
+
+def _write_frame(img, content_img, path, original_colors):
+    """_finish_frame for a file that a later step of the same job reads back and that decides what a resumed job skips: the PNG appears
+    under its name only when it is complete."""
+    if original_colors == 1:
+        img = load.original_colors(content_img, img)
+    img.save(path + ".part", format="PNG")
+    os.replace(path + ".part", path)
+
+
+def _vid_img_flow_device(args, output_dir, frames, style_images_big, content_size):
+    """The device-resident temporal loop (_vid_img_flow_device_job) with its background writer: however the job ends, the queued PNGs
+    are written and the first writer error is raised (after the job's own error, if it has one)."""
+    writer, pending = concurrent.futures.ThreadPoolExecutor(max_workers=4), {}
+    try:
+        _vid_img_flow_device_job(args, output_dir, frames, style_images_big, content_size, writer, pending)
+    finally:
+        try:
+            for fut in list(pending.values()):  # surface any error of the background writer
+                fut.result()
+        finally:
+            writer.shutdown()
+
+
+def _surface_finished(pending):
+    """Raise the error of a write that has failed by now, and forget the writes that are done: a frame whose 8-bit image is kept in
+    memory is never read back from its file, so its writer would otherwise be heard only at the end of the job."""
+    for path in [p for p, fut in pending.items() if fut.done()]:
+        pending.pop(path).result()
+
+
+def _vid_img_flow_device_job(args, output_dir, frames, style_images_big, content_size, writer, pending):
+    """_vid_img_flow with everything around optim.optimize on the device (plan field temporal_device = 1): the same files in the same
+    order, the same messages, the same skipping of finished sizes, passes and frames, the same global-RNG draws in the same order.
+    Style images, content frames, pastiche, blend image, warp grid and reliability mask live in HBM: the warp grid, the warp with the
+    temporal blend as its second output and the mask are csrc/warp.hip; rescaling, colour matching and the 8-bit image are csrc/image.hip.
+    Decoded, rescaled content frames are kept per scale and the 8-bit image of every finished frame is kept for whoever reads it back
+    (both bounded by the plan field frame_cache_mb), so a PNG is decoded only when an earlier run wrote it or `--original_colors` changed it
+    on the way out; PNG encoding and colour transfer run on background threads, whose errors surface before a file is read back and at the
+    end of the job.
+    One rule differs from the host loop: a frame starts from what its predecessor's PNG holds - the 8-bit image, whether this run wrote
+    the file or found it - where the host loop hands the fp32 result on and, after skipping finished frames, starts again from the
+    previous pass's file.  So a resumed job writes the bytes an uninterrupted one would have written - as long as no global-RNG draw
+    feeds the frames (`--no_hist_match`, no `--loop`, no `--init random`): a resumed job makes fewer draws before a given frame than the
+    uninterrupted one, so with colour matching on its jitter, and with it the low bits of the result, differ, as they do in the host loop."""
+    import hip
+    passes = max(1, args.passes_per_scale)
+    mode = args.match_histograms
+    style_images_big = [t.cuda() for t in style_images_big]
+    budget = int(plan.get_float("frame_cache_mb") * (1 << 20))
+    written, content_cache = _ByteBudget(budget), _ByteBudget(budget)
+
+    def read_back(path):
+        if path in written:  # this run wrote it: the bytes the file holds
+            return load.preprocess_u8(written[path])
+        if path in pending:  # colour-transferred on the way out: wait for the writer, decode
+            pending.pop(path).result()
+        return load.preprocess_device(path)  # the arithmetic of preprocess_u8 on the file's bytes: the same bits either way
+
+    prev_size = None
+    for size_n, (current_size, num_iters) in enumerate(zip(args.image_sizes, args.num_iters)):
+        nxt = args.image_sizes[min(len(args.image_sizes) - 1, size_n + 1)]
+        if len(glob.glob("%s/%s/*.png" % (output_dir, nxt))) == len(frames):
+            print("Skipping size: %s, already done." % current_size)
+            prev_size = current_size
+            continue
+        print("\nCurrent size {}px".format(current_size))
+        os.makedirs(output_dir + "/" + str(current_size), exist_ok=True)
+        content_cache.clear()
+        content_scale = current_size / max(*content_size)
+        style_images = _scaled_styles(style_images_big, content_scale ** 2 * content_size[0] * content_size[1], args)
+        optim.set_model_args(args, current_size)
+        net, losses = models.load_model(args)
+
+        def content_of(frame):
+            resized = content_cache.get(frame)
+            if resized is None:
+                resized = content_cache[frame] = _resize(load.preprocess(frame).cuda(), scale_factor=content_scale)
+            return match_histogram(resized, style_images_big[0], mode=mode)
+
+        for pass_n in range(passes):
+            chain = None  # the PNG of the frame before this one in this pass, once there is one
+            if args.loop:
+                start_idx = random.randrange(0, len(frames) - 1)
+                frames = frames[start_idx:] + frames[:start_idx]  # rotate frames
+            if len(glob.glob("%s/%s/%s_*.png" % (output_dir, current_size, pass_n + 2))) == len(frames):
+                print(f"Skipping pass: {pass_n + 1}, already done.")
+                frames = list(reversed(frames))
+                continue
+            direction = "forward" if pass_n % 2 == 0 else "backward"
+            pairs = zip(frames + frames[: 11 if args.loop else 1], frames[1:] + frames[: 10 if args.loop else 1])
+            for n, (prev_frame, this_frame) in enumerate(pairs):
+                args.output = "%s/%s/%s_%s.png" % (output_dir, current_size, pass_n + 1, name(this_frame))
+                if os.path.isfile(args.output) and not n >= len(frames):
+                    print("Skipping pass: %s, frame: %s. File already exists." % (pass_n + 1, name(this_frame)))
+                    chain = args.output
+                    continue
+                print("Optimizing... size: %s, pass: %s, frame: %s" % (current_size, pass_n + 1, name(this_frame)))
+                _surface_finished(pending)
+                content_frames = [content_of(f) for f in (prev_frame, this_frame)]
+                stem = f"{output_dir}/flow/{direction}_{name(prev_frame)}_{name(this_frame)}"
+                hw = tuple(int(v) for v in content_frames[0].shape[2:])
+                if size_n == 0 and pass_n == 0:
+                    if args.init == "random":
+                        pastiche = th.randn(content_frames[1].size()).mul(0.001).cuda()
+                    elif args.init == "prev_warp":
+                        pastiche = read_back(chain) if chain else content_frames[0]
+                        flow_map = load.flow_warp_grid_device(stem + ".flo", pastiche.shape[2:])
+                        pastiche = hip.grid_sample_border(pastiche.contiguous(), flow_map)
+                    else:
+                        pastiche = content_frames[1].clone()
+                else:
+                    wrapped = n > len(frames)  # second lap of a looping clip reads this pass's own files
+                    if pass_n == 0:  # last pass of the previous size
+                        src_dir, src_pass = (current_size, pass_n + 1) if wrapped else (prev_size, passes)
+                    else:            # previous pass of this size
+                        src_dir, src_pass = current_size, (pass_n + 1 if wrapped else pass_n)
+                    if chain:
+                        pastiche = read_back(chain)
+                    else:
+                        pastiche = read_back("%s/%s/%s_%s.png" % (output_dir, src_dir, src_pass, name(prev_frame)))
+                        if pass_n == 0:
+                            pastiche = _resize(pastiche, size=hw)
+                    blend_image = read_back("%s/%s/%s_%s.png" % (output_dir, src_dir, src_pass, name(this_frame)))
+                    if pass_n == 0:
+                        blend_image = _resize(blend_image, size=hw)
+                    flow_map = load.flow_warp_grid_device(stem + ".flo", pastiche.shape[2:])
+                    reliable = load.reliable_flow_weighting_device(stem + ".png", pastiche.shape[2:])
+                    # one pass over the previous frame: its warp (the temporal target) and the blended initial image
+                    warp_image, pastiche = hip.grid_sample_border(pastiche.contiguous(), flow_map, blend=blend_image.contiguous(),
+                                                                  blend_a=args.temporal_blend)
+                    optim.set_temporal_targets(net, warp_image, warp_weights=reliable, args=args)
+
+                out = optim.optimize(content_frames[1], style_images, pastiche, num_iters // passes, args, net, losses,
+                                     keep_on_device=True)
+                out = match_histogram(out.detach(), style_images_big[0], mode=mode)
+                u8 = hip.deprocess_u8(out.float().contiguous(), load._MEAN_BGR)
+                img = Image.fromarray(u8.cpu().numpy(), mode="RGB")
+                cimg = load.deprocess(content_frames[1]) if args.original_colors == 1 else None
+                if args.output in pending:  # second lap of a looping clip: the first lap's file is replaced in order
+                    pending.pop(args.output).result()
+                written.pop(args.output, None)
+                if args.original_colors != 1:
+                    written[args.output] = u8
+                pending[args.output] = writer.submit(_write_frame, img, cimg, args.output, args.original_colors)
+                chain = args.output
+            frames = list(reversed(frames))  # the next pass runs the clip the other way
+        prev_size = current_size
+        del net
+        th.cuda.empty_cache()
 
 
 def vid_img(args):

@@ -48,7 +48,7 @@ def main():
                  L.maua_conv_kxk_x3_bank_bytes(cout, cin, k), L.maua_gram_workspace_bytes(cin, h * w if abs(h * w) < 1 << 40 else 1),
                  L.maua_reduce_workspace_bytes(h * w), L.maua_lbfgs_state_bytes(h * w, rng.choice([1, 5, 100, 254, 255, 0, -1])),
                  L.maua_channel_stats_workspace_bytes(h, w), L.maua_loss_ledger_bytes(n, cin),
-                 L.maua_conv_image_bank_bytes(cout, cin)]
+                 L.maua_conv_image_bank_bytes(cout, cin), L.maua_flow_warp_grid_workspace_bytes(h, w)]
         assert all(s >= 0 for s in sizes)
         if min(n, cin, cout, h, w) <= 0:
             assert sizes[1] == 0 and sizes[2] == 0 and sizes[3] == 0, (n, cin, cout, h, w, sizes)
@@ -100,9 +100,16 @@ def main():
             L.maua_resize_bilinear(ptr, ptr, n, h, w, cout, cin, 0.5, 0.5, None),
             L.maua_channel_stats(ptr, None, 1e-3, n, rng.randint(-1, 3), h, w, ptr, ptr, ws_bytes, None),
             L.maua_lbfgs_iterate(ptr, ptr, ptr, None, h * w, rng.choice([1, 100, 254, 255]), 1.0, -1.0, -1.0, None),
+            L.maua_flow_warp_grid(ptr, ptr, h, w, cout, cin, ptr, ws_bytes, None),
+            L.maua_grid_sample_border(ptr, ptr, ptr, n, cin, h, w, cout, k, (None, ptr)[case % 2], 0.5, (None, ptr)[case // 2 % 2], None),
+            L.maua_mask_u8_resize(ptr, ptr, h, w, (1, 3, 4, 0, 7)[case % 5], cout, cin, None),
         ]
         if min(n, cin, cout, h, w) <= 0:  # (the 1x1 entry takes the product h * w, which two negative extents make positive)
             assert all(rc < 0 for rc in rcs[:11]), (n, cin, cout, h, w, rcs)
+        if min(h, w) <= 0:  # the temporal path (csrc/warp.hip): no workspace for, and no launch over, an empty plane
+            assert sizes[16] == 0 and rcs[-3] < 0 and rcs[-2] < 0 and rcs[-1] < 0, (h, w, sizes[16], rcs[-3:])
+        if min(cout, cin) <= 0:  # ... or onto an empty output (their output extents in these calls)
+            assert rcs[-3] < 0 and rcs[-1] < 0, (cout, cin, rcs[-3:])
         checked += len(rcs) + len(sizes)
     L.maua_set_split_batch_hint(1)
     print(f"fuzz_abi_host: {n_cases} cases, {checked} calls, no sanitizer report, return codes consistent")
