@@ -129,6 +129,8 @@ struct ConvArgs {
     unsigned* arrive;    // split-K finished INSIDE the launch (conv_x3q / conv_x3w, round 6), nullable: one arrival counter per (image, channel
                          //   tile, pixel tile), all zero between launches; the workgroup that draws the last ticket of its tile adds the other
                          //   splits' slabs to its own sums in split order and runs the one-pass epilogue (no conv_splitk_finish launch)
+    int mask_bits;       // conv_x3w with dbank and omask, ksplit <= 1: 1 = the epilogue's ReLU mask is the bits omask > 0 that the Gram phase recorded
+                         //   from its own operand loads (the same values, the same comparison), 0 = the epilogue loads omask (tuning gram_mask_reuse)
 };
 // conv_api.hip: the arrival counters of the workspace the calling host thread armed (maua_conv_arm_workspace) if `workspace` is that one,
 // else null.  ARRIVE_COUNTERS words; a launch that needs more, or whose workspace is another one, finishes its split in a second launch.

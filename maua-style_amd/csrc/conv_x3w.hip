@@ -24,6 +24,8 @@
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace maua {
@@ -178,6 +180,17 @@ __global__ void __launch_bounds__(1024) pack_dmat_x3w_batch_kernel(DmatPackBatch
     } while (0)
 #else
 #define XW_MARK(k) do {} while (0)
+#endif
+#ifdef XW_STAMP
+#define XW_END_STAMP()                                                                                      \
+    do { /* end of the epilogue, its stores drained: slot 63, word 6 */                                     \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                    \
+        if (lane == 0 && p.mask)                                                                            \
+            const_cast<float*>(p.mask)[((((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 64 + 63) * 8 + 6] = \
+                __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_s_memtime());                          \
+    } while (0)
+#else
+#define XW_END_STAMP() do {} while (0)
 #endif
 
 // UNPOOL: `x` is the POOLED map of a 2x2 / 2 max pool and `in_codes` its decision bytes; the input the convolution sees is the pool's
@@ -578,15 +591,27 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
         }
     }
 
+#ifdef XW_STAMP
+    if (lane == 0 && p.mask) {  // end of the K loop: slot 63, word 5
+        float* d_ = const_cast<float*>(p.mask) + ((((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + wave) * 64 + 63) * 8;
+        d_[5] = __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_s_memtime());
+    }
+#endif
     // Fused Gram backward: the 16-channel chunks of F against the matching columns of D - one tap, 12 MFMAs per chunk and wave.
     // Nothing here goes through LDS: a lane's MFMA operands are exactly what it can load itself - its pixel column of its two
     // rows for 8 channels (B operand: 16 coalesced dword loads), its output channel's 8 values of D (A operand: one 16-byte
     // load per part and channel half from the packed bank) - and the power-of-two scale is per WAVE (its own maximum, its own
     // accumulators).  No barrier, no cross-wave exchange: the waves drift apart and hide each other's load latency, the loads
     // of chunk c + 1 are in flight while chunk c is multiplied.
+    //
+    // The masked epilogue needs one bit, F > 0, of F at this lane's pixels for the tile's 64 channels - values the chunks co0 / 16 ... + 3
+    // bring into the wave anyway when the workgroup runs the whole list: lane (half, j) loads channels 16 c2 + 8 half + 0 ... 7, the
+    // epilogue's lane (half, j) stores channels co0 + 32 t + 8 q + 4 half + i = chunk co0 / 16 + 2 t + (q >> 1), octet q & 1, channel
+    // 4 half + i of the octet.  The comparison is made here (fbits: bit 8 k + c of row's word = channel c of this lane's octet of the
+    // tile's k-th chunk), lane ^ 32 - the same pixel column, the other octet - supplies the other half before the epilogue.
+    [[maybe_unused]] unsigned fbits[2] = {0u, 0u};
+    [[maybe_unused]] const bool mask_from_bits = OM && p.mask_bits != 0;  // (wave-uniform; the host sets it only for a whole list: ksplit <= 1)
     if constexpr (!POOL) if (d_begin < nchunks) {
-        __builtin_amdgcn_s_barrier();  // (every wave is done with the LDS fragments of the last 3x3 chunk - nothing below needs LDS,
-                                       //  but the stamps / a later reader of this code should not have to wonder)
         unsigned voff_f[2];
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
@@ -611,7 +636,25 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
 #pragma unroll
                 for (int t = 0; t < 2; ++t) d.a[part][t] = *reinterpret_cast<const u32x4*>(g + part * 2048 + t * 512);
         };
-        auto multiply = [&](DChunk& d) {
+        const int c2_begin = d_begin - nmain, c2_end = nchunks - nmain;  // (this split's part of F)
+        DChunk da, db;
+        request(da, c2_begin);  // (before the barrier: the loads travel while the waves gather; asked for inside the K loop's last pass, the
+                                //  chunk's 32 registers count as live through the whole loop and the kernel spills)
+        __builtin_amdgcn_s_barrier();  // (every wave is done with the LDS fragments of the last 3x3 chunk - nothing below needs LDS,
+                                       //  but the stamps / a later reader of this code should not have to wonder)
+        auto multiply = [&](DChunk& d, int c2) {
+            if constexpr (OM) {
+                const unsigned k = (unsigned)(c2 - (co0 >> 4));
+                if (mask_from_bits && k < 4u) {
+#pragma unroll
+                    for (int row = 0; row < 2; ++row) {
+                        unsigned b8 = 0;
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) b8 |= d.f[row][c] > 0.f ? 1u << c : 0u;  // (the epilogue's comparison: -0, +0 and NaN give 0)
+                        fbits[row] |= b8 << (8 * k);
+                    }
+                }
+            }
             float m = 0.f;
 #pragma unroll
             for (int row = 0; row < 2; ++row)
@@ -653,14 +696,12 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
                         acc[t][row][q] = 0.f;
                     }
         };
-        DChunk da, db;
-        request(da, d_begin - nmain);
-        for (int ch = d_begin; ch < nchunks; ch += 2) {
-            if (ch + 1 < nchunks) request(db, ch + 1 - nmain);
-            multiply(da);
-            if (ch + 1 < nchunks) {
-                if (ch + 2 < nchunks) request(da, ch + 2 - nmain);
-                multiply(db);
+        for (int c2 = c2_begin; c2 < c2_end; c2 += 2) {
+            if (c2 + 1 < c2_end) request(db, c2 + 1);
+            multiply(da, c2);
+            if (c2 + 1 < c2_end) {
+                if (c2 + 2 < c2_end) request(da, c2 + 2);
+                multiply(db, c2 + 1);
             }
         }
     }
@@ -784,59 +825,84 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
     float* __restrict__ yout = p.y + (int64_t)n * p.Cout * out_plane;
     const float* __restrict__ om = p.omask ? p.omask + (int64_t)n * p.Cout * out_plane : nullptr;
     const int ox = x0 + j;
+    // BITS: the ReLU mask comes from the Gram phase's comparisons instead of 64 loads of F: ebits[row][o] = the bits of the octets the
+    // lanes of half o loaded (this lane's own word or lane ^ 32's), shifted so that bit 8 (2 t + (q >> 1)) + i is register 4 q + i's.
+    auto store_rows = [&](auto reuse) {
+        constexpr bool BITS = decltype(reuse)::value;
+        [[maybe_unused]] unsigned ebits[2][2];
+        if constexpr (BITS) {
 #pragma unroll
-    for (int row = 0; row < 2; ++row) {
-        const int oy = y0 + 2 * wave + row;
-        const bool pvalid = oy < p.OH && ox < p.OW;
-        const int64_t opix = (int64_t)oy * p.OW + ox;
-        if (!final_sums) {  // split-K: un-scaled partial sums, finished by conv_splitk_finish_kernel in split order
-            float* wsp = p.ws + (int64_t)blockIdx.z * p.Cout * out_plane;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    if (pvalid && co < p.Cout) wsp[(int64_t)co * out_plane + opix] = master[t][row][r];
-                }
-            continue;
+            for (int row = 0; row < 2; ++row) {
+                const unsigned other = (unsigned)__builtin_amdgcn_ds_bpermute((lane ^ 32) << 2, (int)fbits[row]);
+                ebits[row][0] = (half ? other : fbits[row]) >> (4 * half);
+                ebits[row][1] = (half ? fbits[row] : other) >> (4 * half);
+            }
         }
-        if (!pvalid) continue;
-        const bool full = co0 + XW_COT <= p.Cout;
-        const int64_t lane_off = (int64_t)(co0 + 4 * half) * out_plane + opix;
-        float* __restrict__ yl = yout + lane_off;
-        const float* __restrict__ oml = OM ? om + lane_off : nullptr;
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            float prev[16], msk[16];
+        for (int row = 0; row < 2; ++row) {
+            const int oy = y0 + 2 * wave + row;
+            const bool pvalid = oy < p.OH && ox < p.OW;
+            const int64_t opix = (int64_t)oy * p.OW + ox;
+            if (!final_sums) {  // split-K: un-scaled partial sums, finished by conv_splitk_finish_kernel in split order
+                float* wsp = p.ws + (int64_t)blockIdx.z * p.Cout * out_plane;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cr = t * 32 + (r & 3) + 8 * (r >> 2);
-                const int64_t o = (full || co0 + cr + 4 * half < p.Cout) ? (int64_t)cr * out_plane : 0;
-                prev[r] = 0.f;
-                msk[r] = 1.f;
-                if constexpr (ACC) prev[r] = yl[o];
-                if constexpr (OM) msk[r] = oml[o];
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int co = co0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                        if (pvalid && co < p.Cout) wsp[(int64_t)co * out_plane + opix] = master[t][row][r];
+                    }
+                continue;
             }
-            float outv[16];
+            if (!pvalid) continue;
+            const bool full = co0 + XW_COT <= p.Cout;
+            const int64_t lane_off = (int64_t)(co0 + 4 * half) * out_plane + opix;
+            float* __restrict__ yl = yout + lane_off;
+            const float* __restrict__ oml = OM ? om + lane_off : nullptr;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = master[t][row][r];
-                v += prev[r];
-                if (p.relu) v = v > 0.f ? v : 0.f;
-                outv[r] = msk[r] > 0.f ? v : 0.f;
-            }
-            if (full) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) yl[(int64_t)(t * 32 + (r & 3) + 8 * (r >> 2)) * out_plane] = outv[r];
-            } else {
+            for (int t = 0; t < 2; ++t) {
+                float prev[16], msk[16];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int cr = t * 32 + (r & 3) + 8 * (r >> 2);
-                    if (co0 + cr + 4 * half < p.Cout) yl[(int64_t)cr * out_plane] = outv[r];
+                    const int64_t o = (full || co0 + cr + 4 * half < p.Cout) ? (int64_t)cr * out_plane : 0;
+                    prev[r] = 0.f;
+                    msk[r] = 1.f;
+                    if constexpr (ACC) prev[r] = yl[o];
+                    if constexpr (OM && !BITS) msk[r] = oml[o];
+                }
+                float outv[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = master[t][row][r];
+                    v += prev[r];
+                    if (p.relu) v = v > 0.f ? v : 0.f;
+                    bool keep = msk[r] > 0.f;
+                    if constexpr (BITS) keep = ((ebits[row][(r >> 2) & 1] >> (8 * (2 * t + (r >> 3)) + (r & 3))) & 1u) != 0;
+                    outv[r] = keep ? v : 0.f;
+                }
+                if (full) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) yl[(int64_t)(t * 32 + (r & 3) + 8 * (r >> 2)) * out_plane] = outv[r];
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int cr = t * 32 + (r & 3) + 8 * (r >> 2);
+                        if (co0 + cr + 4 * half < p.Cout) yl[(int64_t)cr * out_plane] = outv[r];
+                    }
                 }
             }
         }
+    };
+    if constexpr (OM) {
+        if (mask_from_bits) {
+            store_rows(std::true_type{});
+            XW_END_STAMP();
+            return;
+        }
     }
+    store_rows(std::false_type{});
+    XW_END_STAMP();
 }
 
 // split-K over 16-channel chunks when the grid leaves most of the 512 workgroup slots (2 per CU) empty
@@ -902,6 +968,9 @@ int conv_x3w_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream)
     {
         p.stagger = (int)tuning("x3w_stagger", 7);
     }
+    // the masked epilogue of a Gram-carrying launch takes its mask bits from the Gram phase's registers when the workgroup runs the whole
+    // chunk list (a split list, the in-launch finish included, loads the mask as before); gram_mask_reuse = 0 forces the loads
+    p.mask_bits = (ks == 1 && a.dbank && om && tuning("gram_mask_reuse", 1) != 0) ? 1 : 0;
     if (a.pool_codes && whole) hipLaunchKernelGGL((conv_x3w_kernel<false, false, true>), grid, dim3(256), 0, stream, p, w_inv);
     else if (a.in_codes && om) hipLaunchKernelGGL((conv_x3w_kernel<false, true, false, true>), grid, dim3(256), 0, stream, p, w_inv);
     else if (a.in_codes) hipLaunchKernelGGL((conv_x3w_kernel<false, false, false, true>), grid, dim3(256), 0, stream, p, w_inv);
