@@ -388,6 +388,26 @@ def test_plan_cache_follows_the_environment(monkeypatch):
     assert plan.get("conv_x3") == "1"
 
 
+def test_every_library_tuning_constant_has_a_test_of_its_other_setting():
+    """Every "lib" field of plan.FIELDS is either forced to non-default values by tests/test_tuning_variants_gpu.py (`VARIANTS`) or named
+    with the existing test that forces it (`COVERED_ELSEWHERE`) - in exactly one of the two tables; the named tests exist, and no value
+    listed as a variant is the field's default.  A tuning constant added without a test of its other setting fails here."""
+    import re
+    import plan
+    import test_tuning_variants_gpu as tv
+    lib_fields = {k for k, (_, who, _) in plan.FIELDS.items() if who == "lib"}
+    assert not set(tv.VARIANTS) & set(tv.COVERED_ELSEWHERE)
+    assert set(tv.VARIANTS) | set(tv.COVERED_ELSEWHERE) == lib_fields
+    for field, values in tv.VARIANTS.items():
+        assert len(values) > 0 and all(float(v) != float(plan.FIELDS[field][0]) for v in values), field
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for field, where in tv.COVERED_ELSEWHERE.items():
+        path, name = where.split("::")
+        text = open(os.path.join(repo, path)).read()
+        assert re.search(rf"^def {re.escape(name)}\(", text, re.M), where
+        assert field in text, where
+
+
 def test_bench_line_refuses_a_stopped_optimiser():
     """bench.lbfgs_still_moving: the timed region's rate is only valid if every iteration did its whole work - a raised stop flag makes the
     update kernels return early.  The helper reports {n_iter, stopped, history_len} and raises when a stop rule fired
