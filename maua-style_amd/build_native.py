@@ -36,7 +36,8 @@ def _file_flags(src):
 def _digest():
     h = hashlib.sha256()
     inc = os.path.join(os.path.dirname(HERE), "include", "maua_hip.h")
-    for p in _sources() + [os.path.join(CSRC, "common.hpp"), inc]:
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
+    for p in _sources() + headers + [inc]:
         with open(p, "rb") as f:
             h.update(p.encode() + b"\0" + f.read())
     return h.hexdigest()

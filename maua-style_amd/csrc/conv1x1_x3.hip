@@ -13,27 +13,14 @@
 // steps per 16 staged values per thread); what it buys is the fp32 matrix cores' 16x lower rate out of the way.
 
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
-#include "common.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int P1_COT = 64, P1_PX = 128, P1_KC = 32;
 constexpr int P1_X_BYTES = 2 * 4 * P1_PX * 16;   // 16384
 constexpr int P1_W_BYTES = 4 * 2 * P1_COT * 16;  // 8192
 
-__device__ __forceinline__ unsigned p1_cvt_pk_f16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float p1_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
-__device__ __forceinline__ float p1_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
 // scale that brings `m` into [2^target, 2^(target+1)); returns the scale, *inv = its inverse (both powers of two)
 __device__ __forceinline__ float p1_scale(float m, int target, float* inv) {
     int e = (int)((__builtin_bit_cast(unsigned, m) >> 23) & 0xffu) - 127;

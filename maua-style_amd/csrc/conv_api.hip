@@ -3,7 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "common.hpp"
+#include "conv_host.hpp"
 
 using namespace maua;
 
@@ -84,13 +84,8 @@ void maua_set_split_batch_hint(int frames) { maua::g_split_batch_hint = frames >
 int maua_get_split_batch_hint(void) { return maua::g_split_batch_hint; }
 
 size_t maua_conv_workspace_bytes(int n, int cin, int h, int w, int cout, int kh, int kw, int stride, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad) || kh <= 0 || kw <= 0 || kh > 64 || kw > 64 || stride <= 0 || stride > 64) return 0;
-    if (!mfma_geometry(kh, kw, stride) || h + 2 * pad < kh || w + 2 * pad < kw) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - kh + 1;
-    a.OW = w + 2 * pad - kw + 1;
+    ConvArgs a;
+    if (!mfma_geometry(kh, kw, stride) || conv_geometry(a, n, cin, h, w, cout, kh, pad) != CONV_SHAPE_OK) return 0;
     if (kh == 3 && cout <= 4 && cin >= 16) return 0;  // few-output-channel kernel: no split
     const int ks = conv_mfma2_choose_split(a, kh, n);
     return ks > 1 ? (size_t)n * ks * cout * a.OH * a.OW * sizeof(float) : 0;
@@ -109,23 +104,16 @@ int maua_conv2d_fwd(const float* x, const float* in_mask, const float* wf, const
     MAUA_REQUIRE((int64_t)h * w < (1ll << 31) && (int64_t)oh * ow < (1ll << 31), MAUA_E_UNSUPPORTED,
                  "conv2d_fwd: plane too large");
     if (mfma_geometry(kh, kw, stride)) {
-        ConvArgs a{};
+        ConvArgs a;
+        conv_geometry(a, n, cin, h, w, cout, kh, pad);  // (checked above: the oh x ow plane)
         a.x = x;
         a.mask = in_mask;
         a.w = wf;
         a.bias = bias;
         a.y = y;
-        a.Cin = cin;
-        a.H = h;
-        a.W = w;
-        a.Cout = cout;
-        a.OH = oh;
-        a.OW = ow;
-        a.pad = pad;
         a.relu = relu;
         a.accumulate = accumulate;
-        a.ws = (workspace && workspace_bytes >= maua_conv_workspace_bytes(n, cin, h, w, cout, kh, kw, stride, pad))
-                   ? (float*)workspace : nullptr;
+        accept_workspace(a, workspace, workspace_bytes, false, [&] { return maua_conv_workspace_bytes(n, cin, h, w, cout, kh, kw, stride, pad); });
         return conv_route(a, kh, n, (hipStream_t)stream);
     }
     return conv_direct_fwd(x, in_mask, wf, bias, y, n, cin, h, w, cout, oh, ow, kh, kw, stride, pad, relu, accumulate,
@@ -142,26 +130,20 @@ int maua_conv2d_bwd_data(const float* gy, const float* out_mask, const float* wb
     MAUA_REQUIRE(h + 2 * pad >= kh && w + 2 * pad >= kw, MAUA_E_UNSUPPORTED, "conv2d_bwd_data: input smaller than filter");
     if (mfma_geometry(kh, kw, stride) && wb) {
         // gx = conv(gy masked, flipped/transposed bank) with padding k-1-p: a forward conv over the gradient
-        ConvArgs a{};
+        MAUA_REQUIRE(kh - 1 - pad >= 0, MAUA_E_UNSUPPORTED, "conv2d_bwd_data: pad %d > k-1", pad);
+        // backward-data = forward geometry with the channel roles exchanged on the gradient's plane (its output plane is h x w again)
+        ConvArgs a;
+        if (conv_geometry(a, n, cout, oh, ow, cin, kh, kh - 1 - pad) != CONV_SHAPE_OK) {
+            // (a gradient plane beyond the limits its forward shape kept, e.g. h = 2^24 with pad 2: launched with these extents as ever)
+            a.Cin = cout, a.H = oh, a.W = ow, a.Cout = cin, a.OH = h, a.OW = w, a.pad = kh - 1 - pad;
+        }
         a.x = gy;
         a.mask = out_mask;
         a.w = wb;
-        a.bias = nullptr;
         a.omask = in_relu_mask;
         a.y = gx;
-        a.Cin = cout;
-        a.H = oh;
-        a.W = ow;
-        a.Cout = cin;
-        a.OH = h;
-        a.OW = w;
-        a.pad = kh - 1 - pad;
-        a.relu = 0;
         a.accumulate = accumulate;
-        MAUA_REQUIRE(a.pad >= 0, MAUA_E_UNSUPPORTED, "conv2d_bwd_data: pad %d > k-1", pad);
-        // backward-data = forward geometry with the channel roles exchanged on the gradient's plane
-        a.ws = (workspace && workspace_bytes >= maua_conv_workspace_bytes(n, cout, oh, ow, cin, kh, kw, 1, a.pad))
-                   ? (float*)workspace : nullptr;
+        accept_workspace(a, workspace, workspace_bytes, false, [&] { return maua_conv_workspace_bytes(n, cout, oh, ow, cin, kh, kw, 1, a.pad); });
         return conv_route(a, kh, n, (hipStream_t)stream);
     }
     MAUA_REQUIRE(w_oihw, MAUA_E_INVAL, "conv2d_bwd_data: the direct path needs the OIHW weights");

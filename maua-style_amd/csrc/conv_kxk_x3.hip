@@ -8,16 +8,10 @@
 // two taps x 8 channels (lane half h takes tap 2 s + h), the odd last tap runs alone as a K = 8 step.
 // LDS: patch [part][(4 + KS - 1) x (32 + KS - 1) positions][8 ch] + filters [tap][part][co][8 ch].
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
-#include "common.hpp"
+#include "conv_host.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int KX_COT = 64, KX_TR = 4, KX_TC = 32;
 
@@ -312,34 +306,21 @@ using namespace maua;
 extern "C" {
 
 size_t maua_conv_kxk_x3_bank_bytes(int cout_produced, int cin_consumed, int ks) {
-    if (cout_produced <= 0 || cin_consumed <= 0 || ks <= 0 || ks > 16 || cout_produced > (1 << 20) || cin_consumed > (1 << 20)) return 0;
-    const size_t nchunk = (cin_consumed + 7) / 8, ntile = (cout_produced + KX_COT - 1) / KX_COT;
-    return nchunk * ntile * (size_t)ks * ks * 2 * KX_COT * 16;
+    if (ks <= 0 || ks > 16) return 0;
+    return bank_bytes(cout_produced, cin_consumed, 8, KX_COT, (size_t)ks * ks * 2 * KX_COT * 16);
 }
 
 int maua_conv_pack_filters_kxk_x3(const float* w_oihw, void* bank_fwd, void* bank_bwd, int cout, int cin, int ks, float w_scale,
                                   maua_stream_t stream) {
-    MAUA_REQUIRE(w_oihw && (bank_fwd || bank_bwd) && cout > 0 && cin > 0 && cout <= (1 << 20) && cin <= (1 << 20) && ks > 0 && w_scale > 0.f, MAUA_E_INVAL,
-                 "conv_pack_filters_kxk_x3: bad args");
-    for (int backward = 0; backward < 2; ++backward) {
-        void* bank = backward ? bank_bwd : bank_fwd;
-        if (!bank) continue;
-        hipLaunchKernelGGL(pack_kxk_x3_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw,
-                           (unsigned short*)bank, cout, cin, ks, backward, w_scale);
-        int rc = check_launch("pack_kxk_x3_kernel");
-        if (rc) return rc;
-    }
-    return MAUA_OK;
+    MAUA_REQUIRE(pack_args_ok(w_oihw, bank_fwd, bank_bwd, cout, cin) && ks > 0 && w_scale > 0.f, MAUA_E_INVAL, "conv_pack_filters_kxk_x3: bad args");
+    return pack_two_banks(bank_fwd, bank_bwd, "pack_kxk_x3_kernel", [&](unsigned short* bank, int backward) {
+        hipLaunchKernelGGL(pack_kxk_x3_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, bank, cout, cin, ks, backward, w_scale);
+    });
 }
 
 size_t maua_conv_kxk_x3_workspace_bytes(int n, int cin, int h, int w, int cout, int ks, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad) || ks <= 0 || ks > 16) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - ks + 1;
-    a.OW = w + 2 * pad - ks + 1;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
+    ConvArgs a;
+    if (ks <= 0 || ks > 16 || conv_geometry(a, n, cin, h, w, cout, ks, pad) != CONV_SHAPE_OK) return 0;
     const int split = kxk_choose_split(a, n);
     return split > 1 ? (size_t)n * split * cout * a.OH * a.OW * sizeof(float) : 0;
 }
@@ -348,28 +329,21 @@ int maua_conv_kxk_x3(const float* x, const void* bank, float w_scale, const floa
                      int n, int cin, int h, int w, int cout, int ks, int pad, int relu, int accumulate, void* workspace,
                      size_t workspace_bytes, maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && y, MAUA_E_INVAL, "conv_kxk_x3: null pointer");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && w_scale > 0.f, MAUA_E_INVAL, "conv_kxk_x3: bad dims");
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 5, pad);  // (the one filter size that is built)
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && w_scale > 0.f, MAUA_E_INVAL, "conv_kxk_x3: bad dims");
     MAUA_REQUIRE(ks == 5, MAUA_E_UNSUPPORTED, "conv_kxk_x3: %dx%d filters (5x5 is built; 3x3 has conv_x3, 1x1 conv1x1_x3)", ks, ks);
     MAUA_REQUIRE(pad >= 0 && pad <= ks - 1, MAUA_E_UNSUPPORTED, "conv_kxk_x3: pad %d", pad);
-    const int oh = h + 2 * pad - ks + 1, ow = w + 2 * pad - ks + 1;
-    MAUA_REQUIRE(oh > 0 && ow > 0, MAUA_E_INVAL, "conv_kxk_x3: input smaller than the filter");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_INVAL, "conv_kxk_x3: input smaller than the filter");
     MAUA_REQUIRE((int64_t)h * w < (1ll << 29), MAUA_E_UNSUPPORTED, "conv_kxk_x3: plane too large");
-    ConvArgs a{};
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = oh;
-    a.OW = ow;
-    a.pad = pad;
     a.relu = relu;
     a.accumulate = accumulate;
-    a.ws = (workspace && workspace_bytes >= maua_conv_kxk_x3_workspace_bytes(n, cin, h, w, cout, ks, pad)) ? (float*)workspace : nullptr;
+    accept_workspace(a, workspace, workspace_bytes, false, [&] { return maua_conv_kxk_x3_workspace_bytes(n, cin, h, w, cout, ks, pad); });
     return conv_kxk_x3_launch<5>(a, n, w_scale, (hipStream_t)stream);
 }
 

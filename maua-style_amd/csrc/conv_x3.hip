@@ -22,16 +22,10 @@
 // meet), so one variant serves every channel count (conv1_1's three channels are a single, partly empty chunk).
 
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
-#include "common.hpp"
+#include "conv_host.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 constexpr int X3_COT = 64;
 constexpr int X3_PH = 4, X3_PR = 6, X3_PC = 34;
@@ -39,14 +33,6 @@ constexpr int X3_NPOS = X3_PR * X3_PC;                    // 204
 constexpr int X3_NPOS_PAD = 208;
 constexpr int X3_PATCH_BYTES = 2 * X3_NPOS_PAD * 16;      // 6656
 constexpr int X3_W_BYTES = 9 * 2 * X3_COT * 16;           // 18432 = 18 planes of 1 KiB: [tap][part][co][16 B]
-
-// two floats -> packed fp16 pair, round to nearest even (bits 15:0 = a)
-__device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float f16_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
-__device__ __forceinline__ float f16_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
 
 // bank[dir][chunk][cotile][tap][part][co][ch] (fp16, pre-scaled by w_scale): fwd: co = output channel, ch = input
 // channel, tap = ky*3+kx; bwd-data: roles swapped and taps flipped.  Zero padding for channels beyond the tensor.
@@ -356,31 +342,16 @@ __global__ void __launch_bounds__(256, 4) conv_x3_kernel(ConvArgs p, float w_inv
     }
 }
 
-// same cost model as conv_x6.hip with this kernel's ~2.7 us per chunk
-static int x3_choose_split(const ConvArgs& a, int n) {
-    const int64_t wgs = (int64_t)((a.OW + 31) / 32) * ((a.OH + X3_PH - 1) / X3_PH) * ((a.Cout + X3_COT - 1) / X3_COT) * split_batch_hint();  // planned frames (see conv_x3w.hip)
-    const int nchunks = (a.Cin + 7) / 8;
-    if (wgs >= 4096 || nchunks < 8) return 1;
-    const double out_mb = (double)split_batch_hint() * a.Cout * a.OH * a.OW * 4.0 / 1e6;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int ks = 1; ks <= 16 && ks <= nchunks / 4; ++ks) {
-        const double rounds = (double)((wgs * ks + 1023) / 1024);
-        double cost = rounds * ((double)((nchunks + ks - 1) / ks) + 2.0) * 2.7;
-        if (ks > 1) cost += (ks + 1) * out_mb / 5.0 + 5.0;
-        if (cost < best_cost * 0.97) {
-            best_cost = cost;
-            best = ks;
-        }
-    }
-    return best;
-}
+// same cost model as conv_x6.hip with this kernel's ~2.7 us per 8-channel chunk and two chunk-times of prologue / epilogue
+static constexpr SplitModel X3_SPLIT = {.rows = X3_PH, .cot = X3_COT, .chunk = 8, .partial_chunk = true, .slots = 1024,
+                                             .no_split_wgs = 4096, .min_chunks = 8, .chunks_per_split = 4, .us_per_chunk = 2.7,
+                                             .prologue_chunks = 2.0, .forced = nullptr, .finish_in_launch = false};
 
 int conv_x3_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream) {
     ConvArgs p = a;
     p.tiles_x = (a.OW + 31) / 32;
-    const int64_t tiles = (int64_t)p.tiles_x * ((a.OH + X3_PH - 1) / X3_PH);
-    const int ks = a.ws ? x3_choose_split(a, n) : 1;
+    const int64_t tiles = conv_tiles(a, X3_PH);
+    const int ks = a.ws ? choose_split(X3_SPLIT, a) : 1;
     p.ksplit = ks;
     const int64_t cot = (a.Cout + X3_COT - 1) / X3_COT, per_xcd = (tiles + 7) / 8;
     dim3 grid((unsigned)(per_xcd * 8), (unsigned)cot, (unsigned)(n * ks));
@@ -408,64 +379,37 @@ using namespace maua;
 extern "C" {
 
 size_t maua_conv_x3_bank_bytes(int cout_produced, int cin_consumed) {
-    if (cout_produced <= 0 || cin_consumed <= 0 || cout_produced > (1 << 20) || cin_consumed > (1 << 20)) return 0;
-    const size_t nchunk = (cin_consumed + 7) / 8, ntile = (cout_produced + X3_COT - 1) / X3_COT;
-    return nchunk * ntile * X3_W_BYTES;
+    return bank_bytes(cout_produced, cin_consumed, 8, X3_COT, X3_W_BYTES);
 }
 
 int maua_conv_pack_filters_x3(const float* w_oihw, void* bank_fwd, void* bank_bwd, int cout, int cin, float w_scale,
                               maua_stream_t stream) {
-    MAUA_REQUIRE(w_oihw && (bank_fwd || bank_bwd) && cout > 0 && cin > 0 && cout <= (1 << 20) && cin <= (1 << 20) && w_scale > 0.f, MAUA_E_INVAL,
-                 "conv_pack_filters_x3: bad args");
-    if (bank_fwd) {
-        hipLaunchKernelGGL(pack_x3_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_fwd, cout,
-                           cin, 0, w_scale);
-        int rc = check_launch("pack_x3_kernel");
-        if (rc) return rc;
-    }
-    if (bank_bwd) {
-        hipLaunchKernelGGL(pack_x3_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_bwd, cout,
-                           cin, 1, w_scale);
-        return check_launch("pack_x3_kernel");
-    }
-    return MAUA_OK;
+    MAUA_REQUIRE(pack_args_ok(w_oihw, bank_fwd, bank_bwd, cout, cin) && w_scale > 0.f, MAUA_E_INVAL, "conv_pack_filters_x3: bad args");
+    return pack_two_banks(bank_fwd, bank_bwd, "pack_x3_kernel", [&](unsigned short* bank, int backward) {
+        hipLaunchKernelGGL(pack_x3_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, bank, cout, cin, backward, w_scale);
+    });
 }
 
 size_t maua_conv_x3_workspace_bytes(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    const int ks = x3_choose_split(a, n);
-    return ks > 1 ? (size_t)n * ks * cout * a.OH * a.OW * sizeof(float) : 0;
+    return query_workspace_bytes(X3_SPLIT, n, cin, h, w, cout, pad);
 }
 
 int maua_conv3x3_x3(const float* x, const void* bank, float w_scale, const float* bias, const float* out_relu_mask, float* y,
                     int n, int cin, int h, int w, int cout, int pad, int relu, int accumulate, void* workspace,
                     size_t workspace_bytes, maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && y && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3: bad dims");
-    MAUA_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, MAUA_E_UNSUPPORTED, "conv3x3_x3: input smaller than the filter");
-    MAUA_REQUIRE((int64_t)h * w < (1ll << 30), MAUA_E_UNSUPPORTED, "conv3x3_x3: plane too large");
-    ConvArgs a{};
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 3, pad);
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3: bad dims");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_UNSUPPORTED, "conv3x3_x3: input smaller than the filter");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = relu;
     a.accumulate = accumulate;
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
+    accept_workspace(a, workspace, workspace_bytes, false, X3_SPLIT, n);
     return conv_x3_launch(a, n, w_scale, (hipStream_t)stream);
 }
 

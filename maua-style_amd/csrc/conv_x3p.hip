@@ -21,16 +21,10 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "conv_host.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 constexpr int XP_COT = 64;
 constexpr int XP_ROWS = 16, XP_PR = 18, XP_PC = 34;
@@ -935,11 +929,10 @@ __global__ void __launch_bounds__(XP_THREADS, 2) conv_x3p_kernel(ConvArgs p, X3p
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-static int x3p_choose_split(const ConvArgs& a, int n) {
+static int x3p_choose_split(const ConvArgs& a) {
     // items = tiles x output-channel tiles x frames; every workgroup walks its share, so a split only pays where the list is shorter than
     // the chip (conv5_1 at 1024 x 1024: 8 x 8 items of 16 chunks)
-    const int64_t items = (int64_t)((a.OW + 31) / 32) * ((a.OH + XP_ROWS - 1) / XP_ROWS) * ((a.Cout + XP_COT - 1) / XP_COT) * split_batch_hint();
-    (void)n;
+    const int64_t items = conv_tiles(a, XP_ROWS) * ((a.Cout + XP_COT - 1) / XP_COT) * split_batch_hint();
     const int nchunks = a.Cin / 32;
     const int forced = (int)tuning("x3p_ks", 0);
     // (every split gets chunks: ks is brought down to the number of non-empty ranges of ceil(nchunks / ks) chunks)
@@ -1003,7 +996,7 @@ int conv_x3p_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream)
     X3pArgs q{};
     q.tiles = p.tiles_x * ((a.OH + XP_ROWS - 1) / XP_ROWS);
     q.ncot = a.Cout / XP_COT;
-    const int ks = a.ws ? x3p_choose_split(a, n) : 1;
+    const int ks = a.ws ? x3p_choose_split(a) : 1;
     q.ksplit = ks;
     p.ksplit = ks;
     q.nmain = a.Cin / 32;
@@ -1061,32 +1054,23 @@ using namespace maua;
 extern "C" {
 
 int maua_conv_x3p_supported(int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(1, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.pad = pad;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    return a.OH > 0 && a.OW > 0 && conv_x3p_supports(a) ? 1 : 0;
+    ConvArgs a;
+    return conv_geometry(a, 1, cin, h, w, cout, 3, pad) == CONV_SHAPE_OK && conv_x3p_supports(a) ? 1 : 0;
 }
 
 int maua_conv_x3p_split(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    return x3p_choose_split(a, n);
+    ConvArgs a;
+    return conv_geometry(a, n, cin, h, w, cout, 3, pad) == CONV_SHAPE_OK ? x3p_choose_split(a) : 0;
 }
 
+// (the persistent kernel never finishes a split inside the launch: the [n][ks][Cout][OH][OW] slabs of conv_splitk_finish)
+static size_t x3p_workspace_bytes(const ConvArgs& a, int n) {
+    const int ks = x3p_choose_split(a);
+    return ks > 1 ? (size_t)n * ks * a.Cout * a.OH * a.OW * sizeof(float) : 0;
+}
 size_t maua_conv_x3p_workspace_bytes(int n, int cin, int h, int w, int cout, int pad) {
-    const int ks = maua_conv_x3p_split(n, cin, h, w, cout, pad);
-    return ks > 1 ? (size_t)n * ks * cout * (h + 2 * pad - 2) * (w + 2 * pad - 2) * sizeof(float) : 0;
+    ConvArgs a;
+    return conv_geometry(a, n, cin, h, w, cout, 3, pad) == CONV_SHAPE_OK ? x3p_workspace_bytes(a, n) : 0;
 }
 
 int maua_conv_x3p_set_max_groups(int groups) {
@@ -1100,12 +1084,13 @@ int maua_conv_x3p_preferred(int n, int cin, int h, int w, int cout, int pad) {
     // two items and more (a launch of one item per workgroup has nothing to overlap: conv_x3q.hip is the same loop with less bookkeeping),
     // and where the list deals out evenly: what a launch loses is the difference between the busiest workgroup's share and the mean, plus
     // the pixels its 16 x 32 tiles cover beyond the plane.  Below the bounds conv_x3q / conv_x3w run.
-    if (!maua_conv_x3p_supported(cin, h, w, cout, pad) || !conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    const int oh = h + 2 * pad - 2, ow = w + 2 * pad - 2;
+    ConvArgs a;
+    if (conv_geometry(a, n, cin, h, w, cout, 3, pad) != CONV_SHAPE_OK || !conv_x3p_supports(a)) return 0;
+    const int oh = a.OH, ow = a.OW;
     const double min_fill = tuning("x3p_min_fill", 0.8);
     const int min_items = (int)tuning("x3p_min_items", 512);
-    const int ks = maua_conv_x3p_split(n, cin, h, w, cout, pad);
-    const int64_t items = (int64_t)((ow + 31) / 32) * ((oh + XP_ROWS - 1) / XP_ROWS) * (cout / XP_COT) * split_batch_hint() * ks;
+    const int ks = x3p_choose_split(a);
+    const int64_t items = conv_tiles(a, XP_ROWS) * (cout / XP_COT) * split_batch_hint() * ks;
     const double fill = (double)items / (double)(((items + 255) / 256) * 256);
     const double cover = (double)oh * ow / ((double)((oh + XP_ROWS - 1) / XP_ROWS * XP_ROWS) * ((ow + 31) / 32 * 32));
     // (a list that is only long enough with the channel loop split is the short-grid case conv_x3q's own split-K form serves as well)
@@ -1117,21 +1102,15 @@ int maua_conv3x3_x3p(const float* x, const unsigned char* in_codes, int honour_r
                      const float* out_relu_mask, const void* dmat_bank, const float* dmat_inv_scale, float* y, unsigned char* pool_codes,
                      int n, int cin, int h, int w, int cout, int pad, int relu, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && y && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3p: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3p: bad dims");
-    MAUA_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, MAUA_E_UNSUPPORTED, "conv3x3_x3p: input smaller than the filter");
-    ConvArgs a{};
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 3, pad);
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3p: bad dims");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_UNSUPPORTED, "conv3x3_x3p: input smaller than the filter");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = relu;
     MAUA_REQUIRE(conv_x3p_supports(a), MAUA_E_UNSUPPORTED,
                  "conv3x3_x3p: needs cin %% 32 == 0, cout %% 64 == 0, cout <= 512, planes of at most 2^24 pixels and an output image below 2 GiB");
@@ -1151,8 +1130,9 @@ int maua_conv3x3_x3p(const float* x, const unsigned char* in_codes, int honour_r
         a.in_codes = in_codes;
         a.in_code_mask = honour_relu_bit ? 7 : 3;
     }
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3p_workspace_bytes(n, cin, h, w, cout, pad) && maua_conv_x3p_split(n, cin, h, w, cout, pad) > 1)
-               ? (float*)workspace : nullptr;
+    size_t need = 0;  // (no split: no workspace)
+    accept_workspace(a, workspace, workspace_bytes, false, [&] { return need = x3p_workspace_bytes(a, n); });
+    if (need == 0) a.ws = nullptr;
     return conv_x3p_launch(a, n, w_scale, (hipStream_t)stream);
 }
 

@@ -34,16 +34,10 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "conv_host.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 constexpr int XQ_COT = 64;
 constexpr int XQ_ROWS = 16, XQ_PR = 18, XQ_PC = 34;
@@ -57,13 +51,6 @@ constexpr int XQ_ITEMS = 4 * XQ_NPOS;            // (octet, position) staging it
 constexpr int XQ_NI = 5;
 constexpr int XQ_THREADS = 512;
 constexpr int XQ_LDS_BYTES = XQ_PATCH_BYTES + XQ_W_BYTES + 64;
-
-__device__ __forceinline__ unsigned xq_cvt_pk_f16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float xq_f16_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
-__device__ __forceinline__ float xq_f16_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
 
 // bank[dir][chunk32][cotile][tap][part][octet][co][ch] (fp16, pre-scaled): fwd: co = output channel, ch = input channel,
 // tap = ky*3+kx; bwd-data: roles swapped and taps flipped.  Zero padding for channels beyond the tensor.
@@ -774,28 +761,12 @@ __global__ void __launch_bounds__(XQ_THREADS, 2) conv_x3q_kernel(ConvArgs p, flo
     XQ_EXIT_STAMP();
 }
 
-// split-K over 32-channel chunks when the grid leaves most of the 256 workgroup slots (1 per CU) empty
-static int x3q_choose_split(const ConvArgs& a, int n) {
-    const int64_t wgs = (int64_t)((a.OW + 31) / 32) * ((a.OH + XQ_ROWS - 1) / XQ_ROWS) * ((a.Cout + XQ_COT - 1) / XQ_COT) * split_batch_hint();
-    (void)n;  // (the policy looks at the frames the job plans per launch, not at this launch's batch: conv_x3w.hip)
-    const int nchunks = a.Cin / 32;
-    const int forced = (int)tuning("x3q_ks", 0);  // experiments: splits every launch k ways (when the layer has the chunks)
-    if (forced > 0) return forced <= nchunks / 2 ? forced : (nchunks >= 4 ? nchunks / 2 : 1);
-    if (wgs >= 1024 || nchunks < 4) return 1;  // (four rounds and more: the tail is small)
-    const double out_mb = (double)split_batch_hint() * a.Cout * a.OH * a.OW * 4.0 / 1e6;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int ks = 1; ks <= 16 && ks <= nchunks / 2; ++ks) {
-        const double rounds = (double)((wgs * ks + 255) / 256);
-        double cost = rounds * ((double)((nchunks + ks - 1) / ks) + 0.7) * 9.0;  // ~9 us per 32-channel chunk of a full CU
-        if (ks > 1) cost += (ks + 1) * out_mb / 5.0 + 5.0;
-        if (cost < best_cost * 0.97) {
-            best_cost = cost;
-            best = ks;
-        }
-    }
-    return best;
-}
+// split-K over 32-channel chunks when the grid leaves most of the 256 workgroup slots (1 per CU) empty: no split from 1024 workgroups
+// (four rounds and more: the tail is small), ~9 us per 32-channel chunk of a full CU, 0.7 chunk-times of prologue; x3q_ks (experiments)
+// splits every launch k ways.  A split finished inside the launch reads (ks - 1) x 128 KiB slabs in one workgroup.
+static constexpr SplitModel XQ_SPLIT = {.rows = XQ_ROWS, .cot = XQ_COT, .chunk = 32, .partial_chunk = false, .slots = 256,
+                                             .no_split_wgs = 1024, .min_chunks = 4, .chunks_per_split = 2, .us_per_chunk = 9.0,
+                                             .prologue_chunks = 0.7, .forced = "x3q_ks", .finish_in_launch = true};
 
 bool conv_x3q_supports(const ConvArgs& a) {
     return a.Cin % 32 == 0 && (int64_t)a.H * a.W <= (1ll << 24) && a.pad >= 0 && a.pad <= 2;
@@ -819,20 +790,6 @@ static int xq_launch_one(const ConvArgs& p, dim3 grid, float w_inv, hipStream_t 
     return check_launch("conv_x3q_kernel");
 }
 
-// Bytes of slabs a launch that finishes its split inside the launch needs: one 128 KiB slab per (image, channel tile, pixel tile, split) - whole
-// tiles, so a little more than the [split][Cout][OH][OW] slabs of the two-launch form on ragged planes.
-static size_t x3q_in_launch_bytes(const ConvArgs& a, int n, int ks) {
-    const int64_t tiles = (int64_t)((a.OW + 31) / 32) * ((a.OH + XQ_ROWS - 1) / XQ_ROWS), cot = (a.Cout + XQ_COT - 1) / XQ_COT;
-    return (size_t)n * cot * tiles * ks * (XQ_COT * XQ_ROWS * 32 * 4);
-}
-// Whether a launch split `ks` ways finishes inside the launch: the caller armed this workspace (a.arrive), the split is small enough for
-// one workgroup to add the other slabs (tuning constant finish_in_launch_max_ks, default 4: it reads (ks - 1) x 128 KiB alone), and the
-// tiles have counters.
-static bool x3q_finish_in_launch(const ConvArgs& a, int n, int ks) {
-    const int64_t units = (int64_t)n * ((a.Cout + XQ_COT - 1) / XQ_COT) * ((a.OW + 31) / 32) * ((a.OH + XQ_ROWS - 1) / XQ_ROWS);
-    return ks > 1 && a.arrive != nullptr && ks <= (int)tuning("finish_in_launch_max_ks", 4) && units <= ARRIVE_COUNTERS;
-}
-
 int conv_x3q_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream) {
     ConvArgs p = a;
 #ifdef XQ_STAMP
@@ -840,12 +797,12 @@ int conv_x3q_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream)
 #endif
     p.tiles_x = (a.OW + 31) / 32;
     p.cot_inner = tuning("cot_inner", 0) != 0 ? 1 : 0;
-    const int64_t tiles = (int64_t)p.tiles_x * ((a.OH + XQ_ROWS - 1) / XQ_ROWS);
-    const int ks = a.ws ? x3q_choose_split(a, n) : 1;
+    const int64_t tiles = conv_tiles(a, XQ_ROWS);
+    const int ks = a.ws ? choose_split(XQ_SPLIT, a) : 1;
     p.ksplit = ks;
     const int64_t cot = (a.Cout + XQ_COT - 1) / XQ_COT, per_xcd = (tiles + 7) / 8;
     dim3 grid((unsigned)(per_xcd * 8), (unsigned)cot, (unsigned)(n * ks));
-    const bool whole = ks == 1 || x3q_finish_in_launch(a, n, ks);  // the launch's epilogue holds complete sums (one pass, or the last arriver's)
+    const bool whole = ks == 1 || finish_in_launch(XQ_SPLIT, a, n, ks);  // the launch's epilogue holds complete sums (one pass, or the last arriver's)
     if (!whole) p.arrive = nullptr;
     const bool acc = whole && a.accumulate != 0, om = whole && a.omask != nullptr;
     const float w_inv = 1.f / w_scale;
@@ -869,68 +826,36 @@ using namespace maua;
 extern "C" {
 
 size_t maua_conv_x3q_bank_bytes(int cout_produced, int cin_consumed) {
-    if (cout_produced <= 0 || cin_consumed <= 0 || cout_produced > (1 << 20) || cin_consumed > (1 << 20)) return 0;
-    const size_t nchunk = (cin_consumed + 31) / 32, ntile = (cout_produced + XQ_COT - 1) / XQ_COT;
-    return nchunk * ntile * XQ_W_BYTES;
+    return bank_bytes(cout_produced, cin_consumed, 32, XQ_COT, XQ_W_BYTES);
 }
 
 int maua_conv_pack_filters_x3q(const float* w_oihw, void* bank_fwd, void* bank_bwd, int cout, int cin, float w_scale,
                                maua_stream_t stream) {
-    MAUA_REQUIRE(w_oihw && (bank_fwd || bank_bwd) && cout > 0 && cin > 0 && cout <= (1 << 20) && cin <= (1 << 20) && w_scale > 0.f, MAUA_E_INVAL,
-                 "conv_pack_filters_x3q: bad args");
-    if (bank_fwd) {
-        hipLaunchKernelGGL(pack_x3q_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_fwd, cout,
-                           cin, 0, w_scale);
-        int rc = check_launch("pack_x3q_kernel");
-        if (rc) return rc;
-    }
-    if (bank_bwd) {
-        hipLaunchKernelGGL(pack_x3q_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_bwd, cout,
-                           cin, 1, w_scale);
-        return check_launch("pack_x3q_kernel");
-    }
-    return MAUA_OK;
+    MAUA_REQUIRE(pack_args_ok(w_oihw, bank_fwd, bank_bwd, cout, cin) && w_scale > 0.f, MAUA_E_INVAL, "conv_pack_filters_x3q: bad args");
+    return pack_two_banks(bank_fwd, bank_bwd, "pack_x3q_kernel", [&](unsigned short* bank, int backward) {
+        hipLaunchKernelGGL(pack_x3q_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, bank, cout, cin, backward, w_scale);
+    });
 }
 
 int maua_conv_x3q_supported(int cin, int h, int w, int pad) {
-    ConvArgs a{};
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.pad = pad;
-    return conv_dims_ok(1, cin, h, w, 1, pad) && conv_x3q_supports(a) ? 1 : 0;
+    ConvArgs a;
+    return conv_geometry(a, 1, cin, h, w, 1, 3, pad) != CONV_SHAPE_BAD_DIMS && conv_x3q_supports(a) ? 1 : 0;
 }
 
 size_t maua_conv_x3q_workspace_bytes(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    const int ks = x3q_choose_split(a, n);
-    if (ks <= 1) return 0;
-    const size_t two_launches = (size_t)n * ks * cout * a.OH * a.OW * sizeof(float);
-    const size_t in_launch = x3q_in_launch_bytes(a, n, ks);  // (whole tiles; a caller that arms its workspace gets this form)
-    return in_launch > two_launches ? in_launch : two_launches;
+    return query_workspace_bytes(XQ_SPLIT, n, cin, h, w, cout, pad);
 }
 
 int maua_conv_x3q_preferred(int n, int cin, int h, int w, int cout, int pad) {
     // One fat workgroup per CU only pays where the grid fills the 256 slots evenly and every workgroup has a K loop long enough to
     // carry its exposed prologue and epilogue (measured, profiles/probes_r04.md section 2: at 724 px - 181 x 181 and 90 x 90 planes,
     // 288 and 432 workgroups - conv_x3w's finer tiles win by 15-20 %; at 1024 / 2048 px the grids are multiples of 256).
-    if (!conv_dims_ok(n, cin, h, w, cout, pad) || cin % 32 != 0) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
+    ConvArgs a;
+    if (conv_geometry(a, n, cin, h, w, cout, 3, pad) != CONV_SHAPE_OK || cin % 32 != 0) return 0;
     const double min_fill = tuning("x3q_min_fill", 0.85);
     const int min_chunks = (int)tuning("x3q_min_chunks", 4);
-    const int ks = x3q_choose_split(a, n);
-    const int64_t wgs = (int64_t)((a.OW + 31) / 32) * ((a.OH + XQ_ROWS - 1) / XQ_ROWS) * ((a.Cout + XQ_COT - 1) / XQ_COT) * split_batch_hint() * ks;
+    const int ks = choose_split(XQ_SPLIT, a);
+    const int64_t wgs = conv_units(XQ_SPLIT, a) * split_batch_hint() * ks;
     const double fill = (double)wgs / (double)(((wgs + 255) / 256) * 256);
     // (ragged tiles count too: the pixels a 16 x 32 tile grid covers beyond the plane)
     const double cover = (double)a.OH * a.OW / ((double)((a.OH + XQ_ROWS - 1) / XQ_ROWS * XQ_ROWS) * ((a.OW + 31) / 32 * 32));
@@ -938,35 +863,22 @@ int maua_conv_x3q_preferred(int n, int cin, int h, int w, int cout, int pad) {
 }
 
 int maua_conv_x3q_split(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    return x3q_choose_split(a, n);
+    return query_split(XQ_SPLIT, n, cin, h, w, cout, pad);
 }
 
 static int conv3x3_x3q_entry(const float* x, const void* bank, float w_scale, const float* bias, const float* out_relu_mask, float* y, int n,
                              int cin, int h, int w, int cout, int pad, int relu, int accumulate, void* workspace, size_t workspace_bytes,
                              maua_stream_t stream, const unsigned char* in_codes = nullptr, int in_code_mask = 0) {
     MAUA_REQUIRE(x && bank && y && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3q: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3q: bad dims");
-    MAUA_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, MAUA_E_UNSUPPORTED, "conv3x3_x3q: input smaller than the filter");
-    ConvArgs a{};
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 3, pad);
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3q: bad dims");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_UNSUPPORTED, "conv3x3_x3q: input smaller than the filter");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = relu;
     a.accumulate = accumulate;
     MAUA_REQUIRE(conv_x3q_supports(a), MAUA_E_UNSUPPORTED, "conv3x3_x3q: needs cin %% 32 == 0 and a plane of at most 2^24 pixels");
@@ -975,8 +887,7 @@ static int conv3x3_x3q_entry(const float* x, const void* bank, float w_scale, co
         a.in_codes = in_codes;
         a.in_code_mask = in_code_mask;
     }
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3q_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
-    a.arrive = a.ws ? armed_counters(workspace) : nullptr;  // (the calling thread armed this workspace: small splits finish inside the launch)
+    accept_workspace(a, workspace, workspace_bytes, true, XQ_SPLIT, n);
     return conv_x3q_launch(a, n, w_scale, (hipStream_t)stream);
 }
 
@@ -991,26 +902,18 @@ int maua_conv3x3_x3q_relu_pool(const float* x, const void* bank, float w_scale, 
                                int n, int cin, int h, int w, int cout, int pad, void* workspace, size_t workspace_bytes,
                                maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && pooled && codes && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3q_relu_pool: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3q_relu_pool: bad dims");
-    ConvArgs a{};
+    ConvArgs a;
+    MAUA_REQUIRE(conv_geometry(a, n, cin, h, w, cout, 3, pad) != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3q_relu_pool: bad dims");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.y = pooled;
     a.pool_codes = codes;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = 1;
     MAUA_REQUIRE(a.OH >= 2 && a.OW >= 2 && cout % 8 == 0 && conv_x3q_supports(a), MAUA_E_UNSUPPORTED,
                  "conv3x3_x3q_relu_pool: needs an output plane of 2 x 2 and more, cin %% 32 == 0, cout %% 8 == 0");
     // without a workspace: one pass over the channels, the epilogue holds complete sums and pools them itself
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3q_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
-    a.arrive = a.ws ? armed_counters(workspace) : nullptr;  // (the calling thread armed this workspace: small splits finish inside the launch)
+    accept_workspace(a, workspace, workspace_bytes, true, XQ_SPLIT, n);
     return conv_x3q_launch(a, n, w_scale, (hipStream_t)stream);
 }
 

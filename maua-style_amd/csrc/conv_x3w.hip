@@ -26,17 +26,10 @@
 
 #include <type_traits>
 
-#include "common.hpp"
+#include "conv_host.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 constexpr int XW_COT = 64;
 constexpr int XW_ROWS = 8, XW_PR = 10, XW_PC = 34;
@@ -46,13 +39,6 @@ constexpr int XW_PLANE = XW_NPOS_PAD * 16;                      // bytes of one 
 constexpr int XW_PATCH_BYTES = 4 * XW_PLANE;                    // [part][octet]
 constexpr int XW_W_BYTES = 9 * 2 * 2 * XW_COT * 16;             // 36 planes of 1 KiB: [tap][part][octet][co][16 B]
 constexpr int XW_ITEMS = 2 * XW_NPOS;                           // (octet, pos) staging items per chunk: 680 = 2.66 per thread
-
-__device__ __forceinline__ unsigned xw_cvt_pk_f16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
-}
-__device__ __forceinline__ float xw_f16_lo(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[0]; }
-__device__ __forceinline__ float xw_f16_hi(unsigned u) { return (float)__builtin_bit_cast(f16x2, u)[1]; }
 
 // bank[dir][chunk16][cotile][tap][part][octet][co][ch] (fp16, pre-scaled): fwd: co = output channel, ch = input channel,
 // tap = ky*3+kx; bwd-data: roles swapped and taps flipped.  Zero padding for channels beyond the tensor.
@@ -142,9 +128,9 @@ __device__ __forceinline__ void pack_dmat_x3w_body(const float* __restrict__ d, 
             const float v[8] = {v0.x * scale, v0.y * scale, v0.z * scale, v0.w * scale, v1.x * scale, v1.y * scale, v1.z * scale, v1.w * scale};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const unsigned H = xw_cvt_pk_f16(v[2 * q], v[2 * q + 1]);
+                const unsigned H = cvt_pk_f16(v[2 * q], v[2 * q + 1]);
                 Hh[q] = H;
-                Ll[q] = xw_cvt_pk_f16(v[2 * q] - xw_f16_lo(H), v[2 * q + 1] - xw_f16_hi(H));
+                Ll[q] = cvt_pk_f16(v[2 * q] - f16_lo(H), v[2 * q + 1] - f16_hi(H));
             }
         }
         unsigned char* base = reinterpret_cast<unsigned char*>(bank) + ((int64_t)chunk * ntile + tile) * 4096 + co * 16;  // [part][octet][co][16 B]
@@ -369,8 +355,8 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float v0 = rp[k][2 * q] * sx, v1 = rp[k][2 * q + 1] * sx;
-            const unsigned H = xw_cvt_pk_f16(v0, v1);
-            const unsigned Lo = xw_cvt_pk_f16(v0 - xw_f16_lo(H), v1 - xw_f16_hi(H));
+            const unsigned H = cvt_pk_f16(v0, v1);
+            const unsigned Lo = cvt_pk_f16(v0 - f16_lo(H), v1 - f16_hi(H));
             hl[dst][0][q] = H;
             hl[dst][1][q] = Lo;
         }
@@ -672,9 +658,9 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float v0 = d.f[row][2 * q] * s, v1 = d.f[row][2 * q + 1] * s;
-                    const unsigned H = xw_cvt_pk_f16(v0, v1);
+                    const unsigned H = cvt_pk_f16(v0, v1);
                     Hh[q] = H;
-                    Ll[q] = xw_cvt_pk_f16(v0 - xw_f16_lo(H), v1 - xw_f16_hi(H));
+                    Ll[q] = cvt_pk_f16(v0 - f16_lo(H), v1 - f16_hi(H));
                 }
                 b[row][0] = __builtin_bit_cast(f16x8, Hh);
                 b[row][1] = __builtin_bit_cast(f16x8, Ll);
@@ -905,30 +891,11 @@ __global__ void __launch_bounds__(256, 2) conv_x3w_kernel(ConvArgs p, float w_in
     XW_END_STAMP();
 }
 
-// split-K over 16-channel chunks when the grid leaves most of the 512 workgroup slots (2 per CU) empty
-static int x3w_choose_split(const ConvArgs& a, int n) {
-    const int64_t wgs = (int64_t)((a.OW + 31) / 32) * ((a.OH + XW_ROWS - 1) / XW_ROWS) * ((a.Cout + XW_COT - 1) / XW_COT) * split_batch_hint();
-    (void)n;  // The policy does not look at THIS launch's batch size but at the number of frames the caller plans to evaluate per
-              // launch (maua_set_split_batch_hint, 1 by default): vid_img's frames are then computed with the same summation
-              // order whether they run one at a time or sixteen together - bit-identical results whatever the grouping.
-    const int nchunks = a.Cin / 16;
-    const int forced = (int)tuning("x3w_ks", 0);  // experiments: splits every launch k ways (when the layer has the chunks)
-    if (forced > 0) return forced <= nchunks / 2 ? forced : (nchunks >= 4 ? nchunks / 2 : 1);
-    if (wgs >= 2048 || nchunks < 4) return 1;
-    const double out_mb = (double)split_batch_hint() * a.Cout * a.OH * a.OW * 4.0 / 1e6;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int ks = 1; ks <= 16 && ks <= nchunks / 2; ++ks) {
-        const double rounds = (double)((wgs * ks + 511) / 512);
-        double cost = rounds * ((double)((nchunks + ks - 1) / ks) + 1.0) * 4.0;  // ~4 us per 16-channel chunk of a full CU
-        if (ks > 1) cost += (ks + 1) * out_mb / 5.0 + 5.0;
-        if (cost < best_cost * 0.97) {
-            best_cost = cost;
-            best = ks;
-        }
-    }
-    return best;
-}
+// split-K over 16-channel chunks when the grid leaves most of the 512 workgroup slots (2 per CU) empty: no split from 2048 workgroups,
+// ~4 us per 16-channel chunk of a full CU, one chunk-time of prologue; x3w_ks (experiments) splits every launch k ways
+static constexpr SplitModel XW_SPLIT = {.rows = XW_ROWS, .cot = XW_COT, .chunk = 16, .partial_chunk = false, .slots = 512,
+                                             .no_split_wgs = 2048, .min_chunks = 4, .chunks_per_split = 2, .us_per_chunk = 4.0,
+                                             .prologue_chunks = 1.0, .forced = "x3w_ks", .finish_in_launch = true};
 
 bool conv_x3w_supports(const ConvArgs& a) {
     return a.Cin % 16 == 0 && (int64_t)a.H * a.W <= (1ll << 25) && a.pad >= 0 && a.pad <= 2;
@@ -939,16 +906,6 @@ static float* g_xw_stamp = nullptr;
 extern "C" void maua_xw_set_stamp_buffer(float* buf) { g_xw_stamp = buf; }
 #endif
 
-// In-launch finish of a split channel loop (conv_x3q.hip): one 64 KiB slab per (image, channel tile, pixel tile, split), whole tiles.
-static size_t x3w_in_launch_bytes(const ConvArgs& a, int n, int ks) {
-    const int64_t tiles = (int64_t)((a.OW + 31) / 32) * ((a.OH + XW_ROWS - 1) / XW_ROWS), cot = (a.Cout + XW_COT - 1) / XW_COT;
-    return (size_t)n * cot * tiles * ks * (XW_COT * XW_ROWS * 32 * 4);
-}
-static bool x3w_finish_in_launch(const ConvArgs& a, int n, int ks) {
-    const int64_t units = (int64_t)n * ((a.Cout + XW_COT - 1) / XW_COT) * ((a.OW + 31) / 32) * ((a.OH + XW_ROWS - 1) / XW_ROWS);
-    return ks > 1 && a.arrive != nullptr && ks <= (int)tuning("finish_in_launch_max_ks", 4) && units <= ARRIVE_COUNTERS;
-}
-
 int conv_x3w_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream) {
     ConvArgs p = a;
 #ifdef XW_STAMP
@@ -956,12 +913,12 @@ int conv_x3w_launch(const ConvArgs& a, int n, float w_scale, hipStream_t stream)
 #endif
     p.tiles_x = (a.OW + 31) / 32;
     p.cot_inner = tuning("cot_inner", 0) != 0 ? 1 : 0;
-    const int64_t tiles = (int64_t)p.tiles_x * ((a.OH + XW_ROWS - 1) / XW_ROWS);
-    const int ks = a.ws ? x3w_choose_split(a, n) : 1;
+    const int64_t tiles = conv_tiles(a, XW_ROWS);
+    const int ks = a.ws ? choose_split(XW_SPLIT, a) : 1;
     p.ksplit = ks;
     const int64_t cot = (a.Cout + XW_COT - 1) / XW_COT, per_xcd = (tiles + 7) / 8;
     dim3 grid((unsigned)(per_xcd * 8), (unsigned)cot, (unsigned)(n * ks));
-    const bool whole = ks == 1 || x3w_finish_in_launch(a, n, ks);  // the launch's epilogue holds complete sums (one pass, or the last arriver's)
+    const bool whole = ks == 1 || finish_in_launch(XW_SPLIT, a, n, ks);  // the launch's epilogue holds complete sums (one pass, or the last arriver's)
     if (!whole) p.arrive = nullptr;
     const bool acc = whole && a.accumulate != 0, om = whole && a.omask != nullptr;
     const float w_inv = 1.f / w_scale;
@@ -991,27 +948,15 @@ using namespace maua;
 extern "C" {
 
 size_t maua_conv_x3w_bank_bytes(int cout_produced, int cin_consumed) {
-    if (cout_produced <= 0 || cin_consumed <= 0 || cout_produced > (1 << 20) || cin_consumed > (1 << 20)) return 0;
-    const size_t nchunk = (cin_consumed + 15) / 16, ntile = (cout_produced + XW_COT - 1) / XW_COT;
-    return nchunk * ntile * XW_W_BYTES;
+    return bank_bytes(cout_produced, cin_consumed, 16, XW_COT, XW_W_BYTES);
 }
 
 int maua_conv_pack_filters_x3w(const float* w_oihw, void* bank_fwd, void* bank_bwd, int cout, int cin, float w_scale,
                                maua_stream_t stream) {
-    MAUA_REQUIRE(w_oihw && (bank_fwd || bank_bwd) && cout > 0 && cin > 0 && cout <= (1 << 20) && cin <= (1 << 20) && w_scale > 0.f, MAUA_E_INVAL,
-                 "conv_pack_filters_x3w: bad args");
-    if (bank_fwd) {
-        hipLaunchKernelGGL(pack_x3w_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_fwd, cout,
-                           cin, 0, w_scale);
-        int rc = check_launch("pack_x3w_kernel");
-        if (rc) return rc;
-    }
-    if (bank_bwd) {
-        hipLaunchKernelGGL(pack_x3w_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_bwd, cout,
-                           cin, 1, w_scale);
-        return check_launch("pack_x3w_kernel");
-    }
-    return MAUA_OK;
+    MAUA_REQUIRE(pack_args_ok(w_oihw, bank_fwd, bank_bwd, cout, cin) && w_scale > 0.f, MAUA_E_INVAL, "conv_pack_filters_x3w: bad args");
+    return pack_two_banks(bank_fwd, bank_bwd, "pack_x3w_kernel", [&](unsigned short* bank, int backward) {
+        hipLaunchKernelGGL(pack_x3w_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, bank, cout, cin, backward, w_scale);
+    });
 }
 
 size_t maua_conv_x3w_dmat_bank_bytes(int c) {
@@ -1048,27 +993,12 @@ int maua_conv_pack_dmat_x3w_batch(int count, const float* const* dmats, const in
 }
 
 int maua_conv_x3w_supported(int cin, int h, int w, int pad) {
-    ConvArgs a{};
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.pad = pad;
-    return conv_dims_ok(1, cin, h, w, 1, pad) && conv_x3w_supports(a) ? 1 : 0;
+    ConvArgs a;
+    return conv_geometry(a, 1, cin, h, w, 1, 3, pad) != CONV_SHAPE_BAD_DIMS && conv_x3w_supports(a) ? 1 : 0;
 }
 
 size_t maua_conv_x3w_workspace_bytes(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    const int ks = x3w_choose_split(a, n);
-    if (ks <= 1) return 0;
-    const size_t two_launches = (size_t)n * ks * cout * a.OH * a.OW * sizeof(float);
-    const size_t in_launch = x3w_in_launch_bytes(a, n, ks);  // (whole tiles; a caller that arms its workspace gets this form)
-    return in_launch > two_launches ? in_launch : two_launches;
+    return query_workspace_bytes(XW_SPLIT, n, cin, h, w, cout, pad);
 }
 
 static int conv3x3_x3w_entry(const float* x, const void* bank, float w_scale, const float* bias, const float* out_relu_mask, float* y,
@@ -1076,21 +1006,15 @@ static int conv3x3_x3w_entry(const float* x, const void* bank, float w_scale, co
                              const float* dinv, void* workspace, size_t workspace_bytes, maua_stream_t stream,
                              const unsigned char* in_codes = nullptr, int in_code_mask = 0) {
     MAUA_REQUIRE(x && bank && y && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3w: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3w: bad dims");
-    MAUA_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, MAUA_E_UNSUPPORTED, "conv3x3_x3w: input smaller than the filter");
-    ConvArgs a{};
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 3, pad);
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3w: bad dims");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_UNSUPPORTED, "conv3x3_x3w: input smaller than the filter");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = relu;
     a.accumulate = accumulate;
     MAUA_REQUIRE(conv_x3w_supports(a), MAUA_E_UNSUPPORTED, "conv3x3_x3w: needs cin %% 16 == 0 and a plane of at most 2^25 pixels");
@@ -1106,8 +1030,7 @@ static int conv3x3_x3w_entry(const float* x, const void* bank, float w_scale, co
         a.in_codes = in_codes;
         a.in_code_mask = in_code_mask;
     }
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3w_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
-    a.arrive = a.ws ? armed_counters(workspace) : nullptr;  // (the calling thread armed this workspace: small splits finish inside the launch)
+    accept_workspace(a, workspace, workspace_bytes, true, XW_SPLIT, n);
     return conv_x3w_launch(a, n, w_scale, (hipStream_t)stream);
 }
 
@@ -1119,40 +1042,25 @@ int maua_conv3x3_x3w(const float* x, const void* bank, float w_scale, const floa
 }
 
 int maua_conv_x3w_split(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    return x3w_choose_split(a, n);
+    return query_split(XW_SPLIT, n, cin, h, w, cout, pad);
 }
 
 int maua_conv3x3_x3w_relu_pool(const float* x, const void* bank, float w_scale, const float* bias, float* pooled,
                                unsigned char* codes, int n, int cin, int h, int w, int cout, int pad, void* workspace,
                                size_t workspace_bytes, maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && pooled && codes && w_scale > 0.f, MAUA_E_INVAL, "conv3x3_x3w_relu_pool: bad args");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x3w_relu_pool: bad dims");
-    ConvArgs a{};
+    ConvArgs a;
+    MAUA_REQUIRE(conv_geometry(a, n, cin, h, w, cout, 3, pad) != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x3w_relu_pool: bad dims");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.y = pooled;
     a.pool_codes = codes;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = 1;
     MAUA_REQUIRE(a.OH >= 2 && a.OW >= 2 && cout % 8 == 0 && conv_x3w_supports(a), MAUA_E_UNSUPPORTED,
                  "conv3x3_x3w_relu_pool: needs an output plane of 2 x 2 and more, cin %% 16 == 0, cout %% 8 == 0");
     // without a workspace: one pass over the channels, the epilogue holds complete sums and pools them itself
-    a.ws = (workspace && workspace_bytes >= maua_conv_x3w_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
-    a.arrive = a.ws ? armed_counters(workspace) : nullptr;  // (the calling thread armed this workspace: small splits finish inside the launch)
+    accept_workspace(a, workspace, workspace_bytes, true, XW_SPLIT, n);
     return conv_x3w_launch(a, n, w_scale, (hipStream_t)stream);
 }
 

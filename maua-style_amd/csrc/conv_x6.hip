@@ -20,7 +20,7 @@
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "conv_host.hpp"
 
 namespace maua {
 
@@ -482,32 +482,17 @@ __global__ void __launch_bounds__(256, 4) conv_x6_kernel(ConvArgs p) {
 
 // Split the K loop over several workgroups when the output grid quantises badly against the chip's 1024 workgroup slots
 // (4 per CU x 256 CUs): e.g. conv4_x of a 724-px image is 552 workgroups - 54 % of one round - and of a 1448-px image
-// 2208 = 2.16 rounds.  Cost model per candidate split: rounds x (chunks per workgroup + 1.5 chunk-times of prologue /
-// epilogue) x 5 us per chunk, plus the finish kernel's traffic (ks partial reads + one write at ~5 TB/s).
-static int x6_choose_split(const ConvArgs& a, int n) {
-    const int64_t wgs = (int64_t)((a.OW + 31) / 32) * ((a.OH + X6_PH - 1) / X6_PH) * ((a.Cout + X6_COT - 1) / X6_COT) * split_batch_hint();  // planned frames (see conv_x3w.hip)
-    const int nchunks = (a.Cin + 7) / 8;
-    if (wgs >= 4096 || nchunks < 8) return 1;
-    const double out_mb = (double)split_batch_hint() * a.Cout * a.OH * a.OW * 4.0 / 1e6;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int ks = 1; ks <= 16 && ks <= nchunks / 4; ++ks) {
-        const double rounds = (double)((wgs * ks + 1023) / 1024);
-        double cost = rounds * ((double)((nchunks + ks - 1) / ks) + 1.5) * 5.0;
-        if (ks > 1) cost += (ks + 1) * out_mb / 5.0 + 5.0;  // finish kernel: MB / (5 TB/s) in us, plus its launch
-        if (cost < best_cost * 0.97) {  // prefer the smaller split unless the gain is real
-            best_cost = cost;
-            best = ks;
-        }
-    }
-    return best;
-}
+// 2208 = 2.16 rounds.  Cost model per candidate split (conv_host.hpp): rounds x (chunks per workgroup + 1.5 chunk-times of
+// prologue / epilogue) x 5 us per 8-channel chunk, plus the finish kernel's traffic; no split from 4096 workgroups.
+static constexpr SplitModel X6_SPLIT = {.rows = X6_PH, .cot = X6_COT, .chunk = 8, .partial_chunk = true, .slots = 1024,
+                                             .no_split_wgs = 4096, .min_chunks = 8, .chunks_per_split = 4, .us_per_chunk = 5.0,
+                                             .prologue_chunks = 1.5, .forced = nullptr, .finish_in_launch = false};
 
 int conv_x6_launch(const ConvArgs& a, int n, hipStream_t stream) {
     ConvArgs p = a;
     p.tiles_x = (a.OW + 31) / 32;
-    const int64_t tiles = (int64_t)p.tiles_x * ((a.OH + X6_PH - 1) / X6_PH);
-    int ks = a.ws ? x6_choose_split(a, n) : 1;
+    const int64_t tiles = conv_tiles(a, X6_PH);
+    int ks = a.ws ? choose_split(X6_SPLIT, a) : 1;
 #ifdef MAUA_X6_STAMP
     ks = 1;  // the workspace is the stamp buffer in the diagnostic build
 #endif
@@ -554,63 +539,36 @@ using namespace maua;
 extern "C" {
 
 size_t maua_conv_x6_bank_bytes(int cout_produced, int cin_consumed) {
-    if (cout_produced <= 0 || cin_consumed <= 0 || cout_produced > (1 << 20) || cin_consumed > (1 << 20)) return 0;
-    const size_t nchunk = (cin_consumed + 7) / 8, ntile = (cout_produced + X6_COT - 1) / X6_COT;
-    return nchunk * ntile * X6_W_BYTES;
+    return bank_bytes(cout_produced, cin_consumed, 8, X6_COT, X6_W_BYTES);
 }
 
 int maua_conv_pack_filters_x6(const float* w_oihw, void* bank_fwd, void* bank_bwd, int cout, int cin, maua_stream_t stream) {
-    MAUA_REQUIRE(w_oihw && (bank_fwd || bank_bwd) && cout > 0 && cin > 0 && cout <= (1 << 20) && cin <= (1 << 20), MAUA_E_INVAL, "conv_pack_filters_x6: bad args");
-    if (bank_fwd) {
-        hipLaunchKernelGGL(pack_x6_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_fwd,
-                           cout, cin, 0);
-        int rc = check_launch("pack_x6_kernel");
-        if (rc) return rc;
-    }
-    if (bank_bwd) {
-        hipLaunchKernelGGL(pack_x6_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)bank_bwd,
-                           cout, cin, 1);
-        return check_launch("pack_x6_kernel");
-    }
-    return MAUA_OK;
+    MAUA_REQUIRE(pack_args_ok(w_oihw, bank_fwd, bank_bwd, cout, cin), MAUA_E_INVAL, "conv_pack_filters_x6: bad args");
+    return pack_two_banks(bank_fwd, bank_bwd, "pack_x6_kernel", [&](unsigned short* bank, int backward) {
+        hipLaunchKernelGGL(pack_x6_kernel, dim3(1024), dim3(256), 0, (hipStream_t)stream, w_oihw, bank, cout, cin, backward);
+    });
 }
 
 size_t maua_conv_x6_workspace_bytes(int n, int cin, int h, int w, int cout, int pad) {
-    if (!conv_dims_ok(n, cin, h, w, cout, pad)) return 0;
-    ConvArgs a{};
-    a.Cin = cin;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    if (a.OH <= 0 || a.OW <= 0) return 0;
-    const int ks = x6_choose_split(a, n);
-    return ks > 1 ? (size_t)n * ks * cout * a.OH * a.OW * sizeof(float) : 0;
+    return query_workspace_bytes(X6_SPLIT, n, cin, h, w, cout, pad);
 }
 
 int maua_conv3x3_x6(const float* x, const void* bank, const float* bias, const float* out_relu_mask, float* y, int n,
                     int cin, int h, int w, int cout, int pad, int relu, int accumulate, void* workspace,
                     size_t workspace_bytes, maua_stream_t stream) {
     MAUA_REQUIRE(x && bank && y, MAUA_E_INVAL, "conv3x3_x6: null pointer");
-    MAUA_REQUIRE(conv_dims_ok(n, cin, h, w, cout, pad) && pad <= 2, MAUA_E_INVAL, "conv3x3_x6: bad dims");
-    MAUA_REQUIRE(h + 2 * pad >= 3 && w + 2 * pad >= 3, MAUA_E_UNSUPPORTED, "conv3x3_x6: input smaller than the filter");
-    MAUA_REQUIRE((int64_t)h * w < (1ll << 30), MAUA_E_UNSUPPORTED, "conv3x3_x6: plane too large");
-    ConvArgs a{};
+    ConvArgs a;
+    const ConvShape shape = conv_geometry(a, n, cin, h, w, cout, 3, pad);
+    MAUA_REQUIRE(shape != CONV_SHAPE_BAD_DIMS && pad <= 2, MAUA_E_INVAL, "conv3x3_x6: bad dims");
+    MAUA_REQUIRE(shape == CONV_SHAPE_OK, MAUA_E_UNSUPPORTED, "conv3x3_x6: input smaller than the filter");
     a.x = x;
     a.w6 = bank;
     a.bias = bias;
     a.omask = out_relu_mask;
     a.y = y;
-    a.Cin = cin;
-    a.H = h;
-    a.W = w;
-    a.Cout = cout;
-    a.OH = h + 2 * pad - 2;
-    a.OW = w + 2 * pad - 2;
-    a.pad = pad;
     a.relu = relu;
     a.accumulate = accumulate;
-    // split-K only with a big enough workspace; without one the kernel still runs, just with fewer workgroups
-    a.ws = (workspace && workspace_bytes >= maua_conv_x6_workspace_bytes(n, cin, h, w, cout, pad)) ? (float*)workspace : nullptr;
+    accept_workspace(a, workspace, workspace_bytes, false, X6_SPLIT, n);
 #ifdef MAUA_X6_STAMP
     a.ws = (float*)workspace;  // caller provides 64 B per workgroup
 #endif

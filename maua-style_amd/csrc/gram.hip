@@ -8,12 +8,9 @@
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
-#include "common.hpp"
+#include "fp16x3.hpp"
 
 namespace maua {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 
 constexpr int GT = 64;       // tile edge (channels)
 #ifndef MAUA_GRAM_GK
@@ -22,7 +19,6 @@ constexpr int GT = 64;       // tile edge (channels)
 constexpr int GK = MAUA_GRAM_GK;  // pixels per stage
 constexpr int GRS = GK + 4;  // LDS row stride (floats): 16-byte aligned rows, 4*row mod 64 banks -> conflict-free b128
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 
 // Row means in two fixed-order stages: grid (C, splits) partial sums in fp64, then one small kernel adds each row's partials in index
@@ -209,18 +205,9 @@ gram_partial_kernel(const float* __restrict__ f, const float* __restrict__ mean,
 //     32x32 output block therefore sees one scale pair per pixel half: k-steps 0-1 and 2-3 accumulate separately and are
 //     folded with (inverse scale of its row block) x (inverse scale of its column block).
 // Same slab format as gram_partial_kernel, same plan, same finish kernels; error against fp64 as for the fp32 kernel.
-typedef _Float16 g16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 g16x2 __attribute__((ext_vector_type(2)));
-typedef float g32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int gu32x2 __attribute__((ext_vector_type(2)));
 constexpr int GXROW = 144;                       // bytes per fp16 plane row: 64 px * 2 B + 16 (conflict-free b128 reads)
 constexpr int GXPLANE = GT * GXROW;              // one [channel][px] plane of one part
 constexpr int GXBUF = 2 * 2 * GXPLANE + 64;      // [tile][part] planes + 8 inverse scales [tile][block][half]
-
-__device__ __forceinline__ unsigned gx_cvt_pk(float a, float b) {
-    const g32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, g16x2));
-}
 
 // (workgroup `pair_index` of the tile pairs, slab `ks`: blockIdx.x / .y of a single layer's launch, decoded by the batch kernel below)
 __device__ __forceinline__ void gram_x3_partial_body(const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ partial,
@@ -316,12 +303,12 @@ __device__ __forceinline__ void gram_x3_partial_body(const float* __restrict__ f
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float v0 = r4[r][0] * sx, v1 = r4[r][1] * sx, v2 = r4[r][2] * sx, v3 = r4[r][3] * sx;
-            const unsigned h0 = gx_cvt_pk(v0, v1), h1 = gx_cvt_pk(v2, v3);
-            const g16x2 hh0 = __builtin_bit_cast(g16x2, h0), hh1 = __builtin_bit_cast(g16x2, h1);
-            const unsigned l0 = gx_cvt_pk(v0 - (float)hh0[0], v1 - (float)hh0[1]), l1 = gx_cvt_pk(v2 - (float)hh1[0], v3 - (float)hh1[1]);
+            const unsigned h0 = cvt_pk_f16(v0, v1), h1 = cvt_pk_f16(v2, v3);
+            const f16x2 hh0 = __builtin_bit_cast(f16x2, h0), hh1 = __builtin_bit_cast(f16x2, h1);
+            const unsigned l0 = cvt_pk_f16(v0 - (float)hh0[0], v1 - (float)hh0[1]), l1 = cvt_pk_f16(v2 - (float)hh1[0], v3 - (float)hh1[1]);
             unsigned char* dst = buf + (tile_slot * 2) * GXPLANE + (srow + 8 * r) * GXROW + spx * 2;
-            *reinterpret_cast<gu32x2*>(dst) = gu32x2{h0, h1};
-            *reinterpret_cast<gu32x2*>(dst + GXPLANE) = gu32x2{l0, l1};
+            *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
+            *reinterpret_cast<u32x2*>(dst + GXPLANE) = u32x2{l0, l1};
         }
     };
     auto store_stage = [&](int slot, int64_t p0, unsigned char* buf) {
@@ -355,10 +342,10 @@ __device__ __forceinline__ void gram_x3_partial_body(const float* __restrict__ f
             if (!skip) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const g16x8 ah = *reinterpret_cast<const g16x8*>(cur + a_off + q * 32);
-                    const g16x8 al = *reinterpret_cast<const g16x8*>(cur + GXPLANE + a_off + q * 32);
-                    const g16x8 bh = *reinterpret_cast<const g16x8*>(cur + b_off + q * 32);
-                    const g16x8 bl = *reinterpret_cast<const g16x8*>(cur + GXPLANE + b_off + q * 32);
+                    const f16x8 ah = *reinterpret_cast<const f16x8*>(cur + a_off + q * 32);
+                    const f16x8 al = *reinterpret_cast<const f16x8*>(cur + GXPLANE + a_off + q * 32);
+                    const f16x8 bh = *reinterpret_cast<const f16x8*>(cur + b_off + q * 32);
+                    const f16x8 bl = *reinterpret_cast<const f16x8*>(cur + GXPLANE + b_off + q * 32);
                     if (q < 2) {
                         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc0, 0, 0, 0);
                         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc0, 0, 0, 0);
@@ -519,12 +506,12 @@ __device__ __forceinline__ void gram_x3_partial128_body(const float* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float v0 = r4[h][r][0] * sx, v1 = r4[h][r][1] * sx, v2 = r4[h][r][2] * sx, v3 = r4[h][r][3] * sx;
-                    const unsigned h0 = gx_cvt_pk(v0, v1), h1 = gx_cvt_pk(v2, v3);
-                    const g16x2 hh0 = __builtin_bit_cast(g16x2, h0), hh1 = __builtin_bit_cast(g16x2, h1);
-                    const unsigned l0 = gx_cvt_pk(v0 - (float)hh0[0], v1 - (float)hh0[1]), l1 = gx_cvt_pk(v2 - (float)hh1[0], v3 - (float)hh1[1]);
+                    const unsigned h0 = cvt_pk_f16(v0, v1), h1 = cvt_pk_f16(v2, v3);
+                    const f16x2 hh0 = __builtin_bit_cast(f16x2, h0), hh1 = __builtin_bit_cast(f16x2, h1);
+                    const unsigned l0 = cvt_pk_f16(v0 - (float)hh0[0], v1 - (float)hh0[1]), l1 = cvt_pk_f16(v2 - (float)hh1[0], v3 - (float)hh1[1]);
                     unsigned char* dst = buf + (tile_slot * 2) * GX128_PLANE + (srow + 8 * r) * GXROW + (32 * h + spx) * 2;
-                    *reinterpret_cast<gu32x2*>(dst) = gu32x2{h0, h1};
-                    *reinterpret_cast<gu32x2*>(dst + GX128_PLANE) = gu32x2{l0, l1};
+                    *reinterpret_cast<u32x2*>(dst) = u32x2{h0, h1};
+                    *reinterpret_cast<u32x2*>(dst + GX128_PLANE) = u32x2{l0, l1};
                 }
         };
         if (nstages > 0) load_stage(rr[0], p_begin);
@@ -571,13 +558,13 @@ __device__ __forceinline__ void gram_x3_partial128_body(const float* __restrict_
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            g16x8 ah[2], al[2], bh[2], bl[2];
+            f16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
-                ah[a] = *reinterpret_cast<const g16x8*>(buf + a_off + a * 32 * GXROW + q * 32);
-                al[a] = *reinterpret_cast<const g16x8*>(buf + GX128_PLANE + a_off + a * 32 * GXROW + q * 32);
-                bh[a] = *reinterpret_cast<const g16x8*>(buf + b_off + a * 32 * GXROW + q * 32);
-                bl[a] = *reinterpret_cast<const g16x8*>(buf + GX128_PLANE + b_off + a * 32 * GXROW + q * 32);
+                ah[a] = *reinterpret_cast<const f16x8*>(buf + a_off + a * 32 * GXROW + q * 32);
+                al[a] = *reinterpret_cast<const f16x8*>(buf + GX128_PLANE + a_off + a * 32 * GXROW + q * 32);
+                bh[a] = *reinterpret_cast<const f16x8*>(buf + b_off + a * 32 * GXROW + q * 32);
+                bl[a] = *reinterpret_cast<const f16x8*>(buf + GX128_PLANE + b_off + a * 32 * GXROW + q * 32);
             }
             // (the four accumulators in turn: no MFMA waits for the one before it)
 #pragma unroll

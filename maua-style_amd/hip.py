@@ -304,19 +304,26 @@ def conv_pack_filters_x6(w):
     return bf, bb
 
 
-def conv_pack_filters_x3(w):
-    """OIHW 3x3 weights -> (forward bank, backward-data bank, w_scale) of pre-split, pre-scaled fp16 pairs.  w_scale is the
-    power of two that brings max|w| into [32, 64) (one host read of the maximum per weight version)."""
+def _pack_filters_fp16x3(family, w, *ks):
+    """(forward bank, backward-data bank, w_scale) of an fp16x3 family: w_scale is the power of two that brings max|w| into [32, 64)
+    (one host read of the maximum per weight version); `ks`: the filter size, for the family whose entry points take one."""
     import math
     cout, cin = w.shape[:2]
     m = float(w.abs().max())
     w_scale = 2.0 ** (5 - math.floor(math.log2(m))) if m > 0 and math.isfinite(m) else 1.0
     wc = _f32(w, "w").contiguous()
-    bf = torch.empty(lib().maua_conv_x3_bank_bytes(cout, cin), dtype=torch.uint8, device=w.device)
-    bb = torch.empty(lib().maua_conv_x3_bank_bytes(cin, cout), dtype=torch.uint8, device=w.device)
-    _check(lib().maua_conv_pack_filters_x3(_ptr(wc), bf.data_ptr(), bb.data_ptr(), cout, cin, w_scale, _stream()),
-           "maua_conv_pack_filters_x3")
+    bank_bytes = getattr(lib(), f"maua_conv_{family}_bank_bytes")
+    bf = torch.empty(bank_bytes(cout, cin, *ks), dtype=torch.uint8, device=w.device)
+    bb = torch.empty(bank_bytes(cin, cout, *ks), dtype=torch.uint8, device=w.device)
+    _check(getattr(lib(), f"maua_conv_pack_filters_{family}")(_ptr(wc), bf.data_ptr(), bb.data_ptr(), cout, cin, *ks, w_scale, _stream()),
+           f"maua_conv_pack_filters_{family}")
     return bf, bb, w_scale
+
+
+def conv_pack_filters_x3(w):
+    """OIHW 3x3 weights -> (forward bank, backward-data bank, w_scale) of pre-split, pre-scaled fp16 pairs.  w_scale is the
+    power of two that brings max|w| into [32, 64) (one host read of the maximum per weight version)."""
+    return _pack_filters_fp16x3("x3", w)
 
 
 def conv_x3_workspace_bytes(n, cin, h, w, cout, pad):
@@ -336,16 +343,7 @@ def conv3x3_x3(x, bank, w_scale, bias, cout, pad, relu, out=None, out_relu_mask=
 def conv_pack_filters_x3w(w):
     """OIHW 3x3 weights -> (forward bank, backward-data bank, w_scale) for conv_x3w.hip (16-channel chunks; same split and
     the same power-of-two filter scale as conv_pack_filters_x3)."""
-    import math
-    cout, cin = w.shape[:2]
-    m = float(w.abs().max())
-    w_scale = 2.0 ** (5 - math.floor(math.log2(m))) if m > 0 and math.isfinite(m) else 1.0
-    wc = _f32(w, "w").contiguous()
-    bf = torch.empty(lib().maua_conv_x3w_bank_bytes(cout, cin), dtype=torch.uint8, device=w.device)
-    bb = torch.empty(lib().maua_conv_x3w_bank_bytes(cin, cout), dtype=torch.uint8, device=w.device)
-    _check(lib().maua_conv_pack_filters_x3w(_ptr(wc), bf.data_ptr(), bb.data_ptr(), cout, cin, w_scale, _stream()),
-           "maua_conv_pack_filters_x3w")
-    return bf, bb, w_scale
+    return _pack_filters_fp16x3("x3w", w)
 
 
 def conv_x3w_supported(cin, h, w, pad):
@@ -369,16 +367,7 @@ def conv3x3_x3w(x, bank, w_scale, bias, cout, pad, relu, out=None, out_relu_mask
 def conv_pack_filters_x3q(w):
     """OIHW 3x3 weights -> (forward bank, backward-data bank, w_scale) for conv_x3q.hip (32-channel chunks; same split and
     the same power-of-two filter scale as conv_pack_filters_x3)."""
-    import math
-    cout, cin = w.shape[:2]
-    m = float(w.abs().max())
-    w_scale = 2.0 ** (5 - math.floor(math.log2(m))) if m > 0 and math.isfinite(m) else 1.0
-    wc = _f32(w, "w").contiguous()
-    bf = torch.empty(lib().maua_conv_x3q_bank_bytes(cout, cin), dtype=torch.uint8, device=w.device)
-    bb = torch.empty(lib().maua_conv_x3q_bank_bytes(cin, cout), dtype=torch.uint8, device=w.device)
-    _check(lib().maua_conv_pack_filters_x3q(_ptr(wc), bf.data_ptr(), bb.data_ptr(), cout, cin, w_scale, _stream()),
-           "maua_conv_pack_filters_x3q")
-    return bf, bb, w_scale
+    return _pack_filters_fp16x3("x3q", w)
 
 
 def conv_x3q_supported(cin, h, w, pad):
@@ -566,16 +555,7 @@ def conv3x3_x3w_unpool(pooled_x, codes, honour_relu_bit, bank, w_scale, cout, pa
 def conv_pack_filters_kxk_x3(w):
     """OIHW k x k weights -> (forward bank, backward-data bank, w_scale) of pre-split, pre-scaled fp16 pairs (as
     conv_pack_filters_x3, with k*k taps)."""
-    import math
-    cout, cin, ks = w.shape[0], w.shape[1], w.shape[2]
-    m = float(w.abs().max())
-    w_scale = 2.0 ** (5 - math.floor(math.log2(m))) if m > 0 and math.isfinite(m) else 1.0
-    wc = _f32(w, "w").contiguous()
-    bf = torch.empty(lib().maua_conv_kxk_x3_bank_bytes(cout, cin, ks), dtype=torch.uint8, device=w.device)
-    bb = torch.empty(lib().maua_conv_kxk_x3_bank_bytes(cin, cout, ks), dtype=torch.uint8, device=w.device)
-    _check(lib().maua_conv_pack_filters_kxk_x3(_ptr(wc), bf.data_ptr(), bb.data_ptr(), cout, cin, ks, w_scale, _stream()),
-           "maua_conv_pack_filters_kxk_x3")
-    return bf, bb, w_scale
+    return _pack_filters_fp16x3("kxk_x3", w, w.shape[2])
 
 
 def conv_kxk_x3_workspace_bytes(n, cin, h, w, cout, ks, pad):
