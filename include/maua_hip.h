@@ -12,6 +12,8 @@
  *  - every pointer is a caller-allocated DEVICE pointer (e.g. torch.Tensor.data_ptr() of a
  *    contiguous fp32 ROCm tensor) unless a parameter says "host"; the library never allocates,
  *    frees or retains caller memory;
+ *  - an entry point writes only the elements of its output arguments and the first `*_bytes()` bytes of a workspace, bank, ledger or
+ *    state, and its results do not depend on memory outside its inputs (tests/test_containment_gpu.py: guard bands around every buffer);
  *  - tensors are float32, NCHW, contiguous;
  *  - `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream); all work is enqueued
  *    asynchronously on it, nothing synchronises, so calls can be captured into a hipGraph;
