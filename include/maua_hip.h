@@ -467,6 +467,29 @@ int maua_grid_sample_border(const float* x, const float* grid, float* y, int n, 
                             double blend_a, float* init, maua_stream_t stream);
 int maua_mask_u8_resize(const uint8_t* mask_hwc, float* out_chw, int h, int w, int c, int oh, int ow, maua_stream_t stream);
 
+/* ---- img_vid clips on the device (csrc/gauss_wrap.hip; style.img_vid with the plan field clip_device = 1) ----
+ * maua_gauss_wrap: for a contiguous fp32 clip x (t, c, h, w),
+ *     y = scipy.ndimage.gaussian_filter(np.roll(x, -roll_t, axis=0), [sigma_t, 0, sigma_h, sigma_w], mode="wrap")
+ *   - the reference's initial clip (style.py:92-101) and its temporal blend between scales (style.py:134-137).  scipy's rules are kept:
+ *   axes in the order T, H, W; an axis with sigma <= 1e-15 is skipped; radius r = int(4.0 * sigma + 0.5); weights
+ *   exp(-0.5 * j * j / sigma^2), j = -r .. r, divided by their sum, in fp64; every one-dimensional pass sums in fp64 in a fixed tap order
+ *   and rounds to fp32 once, later axes read the fp32 result.  "wrap" is purely periodic: tap j of output i reads (i + j) mod L; where
+ *   2 r + 1 > L the taps are folded onto the L residues once (f[d] = sum of w[j] over j = d (mod L), ascending j) and the pass runs L
+ *   taps.  The weight tables are built by a kernel on the stream.  roll_t is any integer, taken modulo t, and is a frame offset on the
+ *   read side of the first pass (a circular filter commutes with it); with no axis filtered y is the rolled clip bit for bit.  Passes
+ *   alternate between y and the workspace so that the last one writes y; x is never written.  No atomics: reruns are bit-identical.
+ * maua_gauss_wrap_supported: 0 for an extent < 1, more than 2^31 - 1 elements, a negative or non-finite sigma, or a radius above
+ *   MAUA_GAUSS_WRAP_MAX_RADIUS; else 1 (offsets are 64-bit: 48 x 3 x 2048 x 2048 is supported).
+ * maua_gauss_wrap_workspace_bytes: exact - the weight tables (one per filtered axis, min(2 r + 1, L) doubles, padded to 256 bytes) and,
+ *   with two or three filtered axes, one clip of t * c * h * w floats; 0 when unsupported or when no axis is filtered.
+ * maua_gauss_wrap returns MAUA_E_INVAL before any launch for a null x or y, a null workspace where bytes are needed, x == y, a workspace
+ *   that is too small, or an unsupported shape. */
+#define MAUA_GAUSS_WRAP_MAX_RADIUS 4096
+int maua_gauss_wrap_supported(int t, int c, int h, int w, double sigma_t, double sigma_h, double sigma_w);
+size_t maua_gauss_wrap_workspace_bytes(int t, int c, int h, int w, double sigma_t, double sigma_h, double sigma_w);
+int maua_gauss_wrap(const float* x, float* y, int t, int c, int h, int w, double sigma_t, double sigma_h, double sigma_w, int roll_t,
+                    void* workspace, size_t workspace_bytes, maua_stream_t stream);
+
 /* ---- batches of independent frames (vid_img without optical flow, reference style.py:192-290) ---------- */
 /* The library's tuning constants - routing thresholds and experiment switches (which kernel family a shape gets, forced K splits, the
  * 128 x 128 Gram blocks ...): the host side's planner configuration (maua-style_amd/plan.py lists every name with its default and

@@ -91,6 +91,9 @@ SIGNATURES = {
     "maua_flow_warp_grid": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "maua_grid_sample_border": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, ctypes.c_double, c_p, c_p]),
     "maua_mask_u8_resize": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_gauss_wrap_supported": (c_i, [c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "maua_gauss_wrap_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "maua_gauss_wrap": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i, c_p, c_sz, c_p]),
     "maua_set_tuning": (c_i, [ctypes.c_char_p, ctypes.c_double]),
     "maua_get_tuning": (ctypes.c_double, [ctypes.c_char_p, ctypes.c_double]),
     "maua_set_split_batch_hint": (None, [c_i]),
@@ -1089,6 +1092,32 @@ def mask_u8_resize(mask, size):
         raise HipError(f"mask_u8_resize: output {oh}x{ow}")
     out = torch.empty(1, c, oh, ow, device=m.device, dtype=torch.float32)
     _check(lib().maua_mask_u8_resize(_u8(m, "mask"), _ptr(out), h, w, c, oh, ow, _stream()), "maua_mask_u8_resize")
+    return out
+
+
+def gauss_wrap(x, sigmas, roll=0, workspace=None, out=None):
+    """scipy.ndimage.gaussian_filter(np.roll(x, -roll, axis=0), [sigmas[0], 0, sigmas[1], sigmas[2]], mode="wrap") for a (T,C,H,W) device
+    clip: a new tensor (or `out`, which must not be x).  workspace: at least maua_gauss_wrap_workspace_bytes, else one is allocated."""
+    if not x.is_cuda:
+        raise HipError("gauss_wrap: needs a ROCm device tensor (got a CPU tensor): there is no CPU path")
+    if x.dim() != 4:
+        raise HipError(f"gauss_wrap: clip of shape {tuple(x.shape)}, expected (T, C, H, W)")
+    if len(sigmas) != 3:
+        raise HipError(f"gauss_wrap: sigmas {sigmas!r}, expected (sigma_t, sigma_h, sigma_w)")
+    t, c, h, w = (int(v) for v in x.shape)
+    st, sh, sw = (float(v) for v in sigmas)
+    L = lib()
+    if not L.maua_gauss_wrap_supported(t, c, h, w, st, sh, sw):
+        raise HipError(f"gauss_wrap: unsupported clip {tuple(x.shape)} with sigmas {(st, sh, sw)}")
+    need = L.maua_gauss_wrap_workspace_bytes(t, c, h, w, st, sh, sw)
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    elif tuple(out.shape) != tuple(x.shape):
+        raise HipError(f"gauss_wrap: out {tuple(out.shape)} for a clip {tuple(x.shape)}")
+    if workspace is None and need:  # allocated after the result and held until the launches are enqueued: it must not share memory with it
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    wp, wn = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if workspace is not None else (None, 0)
+    _check(L.maua_gauss_wrap(_ptr(_f32(x, "x")), _ptr(_f32(out, "out")), t, c, h, w, st, sh, sw, int(roll) % t, wp, wn, _stream()), "maua_gauss_wrap")
     return out
 
 

@@ -359,14 +359,17 @@ def video_windows(init, styles, window):
             for k, seq in enumerate(seqs)]
 
 
-def _optimize_video(content, styles, init, num_iters, args, net=None, losses=None):
+def _optimize_video(content, styles, init, num_iters, args, net=None, losses=None, keep_on_device=False):
     """optim.optimize for transfer types with '_vid' (reference optim.py:111-255): the pastiche is a clip, optimised
     `gram_frame_window` frames at a time (one batch of B frames through the network: per-frame static style terms and
     the cross-frame dynamic Gram term of StyleLoss.dynamic_loss, loss.py:164-181).  Windows overlap; frames already
     styled by the previous window (and, at the wrap-around, by the first) get their gradient zeroed, and every window is
     written back into the clip through the same wrapping index.  The window of B frames runs through
-    the fused plan (engine.StyleEngine with B > 1: per-frame static Gram terms plus one (B C) x (B C) dynamic Gram)."""
+    the fused plan (engine.StyleEngine with B > 1: per-frame static Gram terms plus one (B C) x (B C) dynamic Gram).
+    `keep_on_device=True` with a device `init`: the clip, the window gather and the write-back stay where `init` lives (no host copy
+    per window) and the device clip is returned; otherwise the clip is a CPU tensor, as in the reference."""
     limit_host_threads()
+    on_device = bool(keep_on_device) and init.is_cuda
     window = int(args.gram_frame_window)
     windows = video_windows(init, styles, window)
     if net is None or losses is None:
@@ -402,9 +405,14 @@ def _optimize_video(content, styles, init, num_iters, args, net=None, losses=Non
                 if end > 0:
                     grad[-end:] = 0
 
+        if on_device:
+            index = index.to(output.device)
         opt = PixelOptimizer(net, losses, output[index], args, planned_iters=num_iters, grad_hook=mask_overlap)
         _run_iterations(opt, num_iters, args, save_offset=w * num_iters, save_total=len(windows[0]) * num_iters)
-        output[index] = opt.x.detach().cpu().to(output.dtype)
+        if on_device:
+            output[index] = opt.x.detach().to(output.dtype)
+        else:
+            output[index] = opt.x.detach().cpu().to(output.dtype)
         del opt
     for mod in losses:
         mod.loss = 0
@@ -455,7 +463,7 @@ def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep
     optim.py:249).  Inputs may already live on the device; `keep_on_device=True` (the workflow drivers of style.py) returns
     the device tensor instead, so that colour matching, rescaling and the next scale run without a host round trip."""
     if "_vid" in args.transfer_type:
-        return _optimize_video(content, styles, init, num_iters, args, net, losses)
+        return _optimize_video(content, styles, init, num_iters, args, net, losses, keep_on_device=keep_on_device)
     limit_host_threads()
     if init.shape[0] != 1:
         raise NotImplementedError("one frame per call (the reference's img_img / vid_img call pattern)")

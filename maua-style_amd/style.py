@@ -125,6 +125,8 @@ def img_vid(args):
     if not _single_rank_only("img_vid"):
         return None
     limit_host_threads()
+    if plan.on("clip_device") and th.cuda.is_available():
+        return _img_vid_device(args)
     style_videos_big = load.process_style_videos(args)
     content_image_big = match_histogram(load.preprocess(args.content), style_videos_big, mode=args.match_histograms)
     video_length = max(v.shape[0] for v in style_videos_big) if args.num_frames == -1 else args.num_frames
@@ -171,6 +173,90 @@ def img_vid(args):
     pastiche = match_histogram(pastiche, style_videos_big, mode=args.match_histograms)
     load.save_tensor_to_file(pastiche, args)
     return pastiche
+
+
+def clip_roll(num_frames):
+    """Frames the clip is rolled by between two scales: the reference's `th.cat((p[7:], p[:7]))` (style.py:134) moves frame 7 to the front
+    of a clip of more than 7 frames and is the identity for a shorter one (p[7:] is empty, p[:7] the whole clip)."""
+    return 7 if num_frames > 7 else 0
+
+
+def _write_clip(frames_u8, directory):
+    """One PNG per frame of an (T, H, W, 3) uint8 array: <directory>/frame_#####.png (host only: runs on the writer threads)."""
+    for t, frame in enumerate(frames_u8):
+        Image.fromarray(frame, mode="RGB").save(f"{directory}/frame_{t:05d}.png")
+
+
+def _img_vid_device(args):
+    """img_vid with the clip in HBM from the first filter to the last frame (plan field clip_device = 1): the same statements in the same
+    order as the host loop above, the same global-RNG draws in the same order (the noise of the initial clip and the colour-matching
+    jitter are drawn on the host and uploaded), the same directories, file names and resume rule.  The initial clip's periodic Gaussian
+    and the roll + temporal blend between two scales are hip.gauss_wrap (csrc/gauss_wrap.hip; the roll is its read offset), rescaling is
+    hip.resize_bilinear, colour matching keeps device tensors where they are, optim.optimize gathers and writes back its windows on the
+    device, and every frame leaves as its 8-bit image (load.deprocess's device arithmetic, 3 bytes per pixel) for the writer threads,
+    which encode the PNGs beside the next scale.  A job that finds every scale and the final clip finished writes nothing."""
+    import hip
+    mode = args.match_histograms
+    style_videos_big = load.process_style_videos(args)
+    content_image_big = match_histogram(load.preprocess(args.content).cuda(), style_videos_big, mode=mode)
+    video_length = max(v.shape[0] for v in style_videos_big) if args.num_frames == -1 else args.num_frames
+    delta_ts = str(args.gram_frame_window).split(",")
+    content_size = np.array(content_image_big.size()[-2:])
+    H, W = (int(v) for v in content_size)
+
+    if args.init == "random":
+        pastiche = (th.randn((video_length, 3, H, W)) * 255).cuda()
+        pastiche = hip.gauss_wrap(pastiche, (video_length, H / 32, W / 32))
+    elif args.init == "content":
+        pastiche = _resize(content_image_big.clone(), size=(H, W)).repeat([video_length, 1, 1, 1])
+        pastiche += (th.randn((video_length, 3, H, W)) * 255).cuda()
+        pastiche = hip.gauss_wrap(pastiche.contiguous(), (video_length, 4, 4))
+    else:
+        pastiche = load.preprocess_video(args.init, args.fps).repeat([video_length, 1, 1, 1]).cuda()
+    pastiche = match_histogram(pastiche, style_videos_big, mode=mode)
+
+    def queue_clip(clip, directory):
+        if clip.shape[0] == 1:  # a one-frame clip is an image file, as load.save_tensor_to_file names it
+            pending.append(writer.submit(load.save_image_to_file, load.deprocess(clip), args, directory))
+            return
+        os.makedirs(directory, exist_ok=True)
+        u8 = th.stack([hip.deprocess_u8(clip[t:t + 1].float().contiguous(), load._MEAN_BGR) for t in range(clip.shape[0])])
+        pending.append(writer.submit(_write_clip, u8.cpu().numpy(), directory))
+
+    writer, pending, computed = concurrent.futures.ThreadPoolExecutor(max_workers=2), [], False
+    try:
+        for i, (current_size, num_iters) in enumerate(zip(args.image_sizes, args.num_iters)):
+            done = f"{args.output}_{current_size}"
+            if os.path.isdir(done) and os.listdir(done):  # resume: a finished scale is reloaded
+                pastiche = load.preprocess_video(done, args.fps).cuda()
+                continue
+            print("\nCurrent size {}px".format(current_size))
+            computed = True
+            args.gram_frame_window = int(delta_ts[min(i, len(delta_ts) - 1)])
+            content_image = _resize(content_image_big, scale_factor=current_size / max(*content_size))
+            style_videos = _scaled_styles(style_videos_big, content_image.shape[2] * content_image.shape[3], args)
+            pastiche = _resize(pastiche, size=tuple(int(v) for v in content_image.shape[2:]))
+
+            pastiche = optim.optimize(content_image, style_videos, pastiche, num_iters, args, keep_on_device=True).detach()
+
+            # the roll by 7 frames (style.py:134-135) and the temporal blend in one pass over the clip; the style clips roll as before
+            blend = args.temporal_blend if args.temporal_blend > 0 else 0.0
+            pastiche = hip.gauss_wrap(pastiche.float().contiguous(), (blend, 0, 0), roll=clip_roll(pastiche.shape[0]))
+            style_videos_big = [th.cat((svb[7:], svb[:7])) for svb in style_videos_big]
+            pastiche = match_histogram(pastiche, style_videos_big, mode=mode)
+            queue_clip(pastiche, done)
+
+        final = str(args.output)
+        if computed or not (os.path.isdir(final) and len(os.listdir(final)) >= pastiche.shape[0]):
+            pastiche = match_histogram(pastiche, style_videos_big, mode=mode)
+            queue_clip(pastiche, final)
+    finally:
+        try:
+            for fut in pending:  # surface any error of the background writer
+                fut.result()
+        finally:
+            writer.shutdown()
+    return pastiche.cpu()
 
 
 def _vid_img_flow(args, output_dir, frames, style_images_big, content_size):
