@@ -325,6 +325,30 @@ int maua_mse_weighted_fwd_bwd(const float* x, const float* weights, const float*
 int maua_gram_bwd(const float* d_sym, const float* f, const float* row_mean, const float* relu_mask, float* gf, int c,
                   int64_t hw, int accumulate, void* workspace, size_t workspace_bytes, maua_stream_t stream);
 
+/* ---- guided Gram matrices: one Gram / covariance matrix per spatial region (gram_guided.hip) ------- */
+/* Spatial control of the style loss (Gatys et al. 2017): `regions` (1 .. 8) guides of one style layer, guides[regions][hw] with values in
+ * [0, 1], weight the columns of f[C][hw]:
+ *     gram[r][C][C] = scale[r] * X_r X_r^T,  X_r[c][p] = guides[r][p] * (f[c][p] - mean[r][c]),
+ *     mean[r][c] = sum_p guides[r][p]^2 f[c][p] / mass[r] when `center` != 0 (covariance form), else 0.
+ * maua_gram_guided_mass: mass[r] = sum_p guides[r][p]^2 (device doubles, fp64, fixed order) - once per set of guides; the caller reads
+ *   it back and prepares scale[regions] (device floats; loss.StyleLoss: 1 / (C mass[r]), and 0 for a region it leaves out).
+ * maua_gram_guided_fwd: scale[r] == 0 marks an INACTIVE region: nothing is computed for it, gram[r] (and mean_out[r]) are exact zeros.
+ *   mass and mean_out[regions][C] (both nullable unless center).  Every matrix is exactly symmetric; split-K over hw with a fixed-order
+ *   fp64 reduction (same inputs, same bits); fp32-MFMA arithmetic.  Stages of 64 pixels on which a region's guide is zero are skipped.
+ *   workspace: maua_gram_guided_workspace_bytes(regions, C, hw) bytes (0 for a refused shape).
+ * maua_gram_guided_bwd: gf[C][hw] (+)= sum_r coef[r] * guides[r][p]^2 * sum_k d_sym[r][k][c] * (f[k][p] - mean[r][k]); d_sym[regions][C][C]
+ *   symmetric matrices, coef[regions] device floats (0 leaves the region out), mean[regions][C] nullable (no centring).  With
+ *   accumulate == 0 every element of gf is written.  One launch, no workspace.
+ * Any C >= 1 (up to 65536) and hw >= 1 (below 2^30); other shapes and region counts return MAUA_E_UNSUPPORTED (maua_gram_guided_supported
+ * answers 0 for them), null pointers MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before any launch. */
+int maua_gram_guided_supported(int regions, int c, int64_t hw);
+size_t maua_gram_guided_workspace_bytes(int regions, int c, int64_t hw);
+int maua_gram_guided_mass(const float* guides, double* mass, int regions, int64_t hw, maua_stream_t stream);
+int maua_gram_guided_fwd(const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
+                         int regions, int c, int64_t hw, int center, void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_gram_guided_bwd(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean, float* gf, int regions,
+                         int c, int64_t hw, int accumulate, maua_stream_t stream);
+
 /* ---- total variation: loss.TVLoss.forward, loss.py:224-233, and its autograd ---------------------- */
 /* loss_out[0] = strength * (sum|dy| + sum|dx|); grad (+)= strength * d/dx.  workspace as for the MSE. */
 int maua_tv_fwd_bwd(const float* x, float* grad, int n, int c, int h, int w, float strength, int accumulate,

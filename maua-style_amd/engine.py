@@ -82,6 +82,8 @@ class StyleEngine:
                 s = _Step("content", m)
                 s.src = act
             elif isinstance(m, loss_mod.StyleLoss):
+                if getattr(m, "guide", None) is not None:
+                    raise UnsupportedNet("guided StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -391,6 +393,8 @@ class StyleEngine:
                         or w.shape[1] not in (1, shapes_src[1]):
                     raise UnsupportedNet("weighted ContentLoss of this shape runs on the module path")
             return True
+        if getattr(m, "guide", None) is not None:  # (guides set after the plan was made)
+            raise UnsupportedNet("guided StyleLoss runs on the module path")
         if m.target.nelement() == 0:
             raise RuntimeError(f"{m.name}: style target not captured")
         if shapes_src[0] == 1 and m.video_style_factor > 0 and m.video_target.nelement() != 0 \

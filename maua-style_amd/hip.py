@@ -70,6 +70,11 @@ SIGNATURES = {
     "maua_mse_fwd_bwd": (c_i, [c_p, c_p, c_p, c_i64, c_f, c_f, c_i, c_i, c_p, c_p, c_sz, c_p]),
     "maua_mse_weighted_fwd_bwd": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_f, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "maua_gram_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_i, c_p, c_sz, c_p]),
+    "maua_gram_guided_supported": (c_i, [c_i, c_i, c_i64]),
+    "maua_gram_guided_workspace_bytes": (c_sz, [c_i, c_i, c_i64]),
+    "maua_gram_guided_mass": (c_i, [c_p, c_p, c_i, c_i64, c_p]),
+    "maua_gram_guided_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_sz, c_p]),
+    "maua_gram_guided_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
     "maua_tv_fwd_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "maua_fill": (c_i, [c_p, c_i64, c_f, c_p]),
     "maua_depth_to_space": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -849,6 +854,56 @@ def gram_bwd(d_sym, f, row_mean, gf, accumulate, workspace=None, relu_mask=None)
     _check(lib().maua_gram_bwd(_ptr(_f32(d_sym, "d")), _ptr(f), _ptr(row_mean), _ptr(relu_mask), _ptr(gf), c, hw, int(accumulate),
                                workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
            "maua_gram_bwd")
+    return gf
+
+
+def gram_guided_workspace_bytes(regions, c, hw):
+    return lib().maua_gram_guided_workspace_bytes(int(regions), int(c), int(hw))
+
+
+def _guides_2d(guides, hw):
+    if guides.dim() < 2 or guides.numel() != guides.shape[0] * hw:
+        raise HipError(f"guides of shape {tuple(guides.shape)} do not cover {hw} pixels per region")
+    return guides.shape[0]
+
+
+def gram_guided_mass(guides, out=None):
+    """guides: (R, HW) or (R, H, W) -> mass (R,) float64 device tensor, mass[r] = sum guides[r]^2 (fixed order)."""
+    r = guides.shape[0]
+    hw = guides.numel() // max(r, 1)
+    if out is None:
+        out = torch.empty(r, dtype=torch.float64, device=guides.device)
+    _check(lib().maua_gram_guided_mass(_ptr(_f32(guides, "guides")), _ptr(out), r, hw, _stream()), "maua_gram_guided_mass")
+    return out
+
+
+def gram_guided_fwd(f, guides, scale, center=False, mass=None, out=None, mean_out=None, workspace=None):
+    """f: (1,C,H,W) or (C,HW); guides: (R,HW) or (R,H,W); scale: (R,) float32 (0 = inactive region); mass: (R,) float64 (needed to
+    centre).  Returns (grams (R,C,C), weighted row means (R,C) or None)."""
+    c = f.shape[1] if f.dim() == 4 else f.shape[0]
+    hw = f.numel() // c
+    r = _guides_2d(guides, hw)
+    if scale.numel() != r or (center and (mass is None or mass.numel() != r or mass.dtype != torch.float64)):
+        raise HipError("gram_guided_fwd: one scale (float32) and, to centre, one mass (float64) per region")
+    if out is None:
+        out = torch.empty(r, c, c, device=f.device, dtype=torch.float32)
+    if center and mean_out is None:
+        mean_out = torch.empty(r, c, device=f.device, dtype=torch.float32)
+    workspace = _ws(workspace, gram_guided_workspace_bytes(r, c, hw), f.device)
+    _check(lib().maua_gram_guided_fwd(_ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(scale, "scale")), _ptr(mass) if center else None,
+                                      _ptr(out), _ptr(mean_out) if center else None, r, c, hw, int(center), workspace.data_ptr(),
+                                      workspace.numel() * workspace.element_size(), _stream()), "maua_gram_guided_fwd")
+    return out, (mean_out if center else None)
+
+
+def gram_guided_bwd(d_sym, f, guides, coef, mean, gf, accumulate):
+    """gf (+)= sum_r coef[r] guides[r]^2 d_sym[r] (f - mean[r]); d_sym: (R,C,C) symmetric, mean: (R,C) or None."""
+    r, c = d_sym.shape[0], d_sym.shape[1]
+    hw = f.numel() // c
+    if _guides_2d(guides, hw) != r or coef.numel() != r or gf.numel() != f.numel() or (mean is not None and mean.numel() != r * c):
+        raise HipError("gram_guided_bwd: shapes of d_sym, guides, coef, mean and gf do not agree")
+    _check(lib().maua_gram_guided_bwd(_ptr(_f32(d_sym, "d")), _ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(coef, "coef")),
+                                      _ptr(_f32(mean, "mean")), _ptr(_f32(gf, "gf")), r, c, hw, int(accumulate), _stream()), "maua_gram_guided_bwd")
     return gf
 
 

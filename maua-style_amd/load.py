@@ -112,6 +112,49 @@ def process_style_images(args):
     return [preprocess(p) for p in paths]
 
 
+# ---------------------------------------------------------------------------------------------------------
+# Region masks of the guided style loss (loss.StyleLoss.guide): colour-coded segmentation images, named by the file-only preset keys
+# "content_mask" and "style_masks" (style.img_img).
+# ---------------------------------------------------------------------------------------------------------
+MAX_REGIONS = 8
+
+
+def read_mask(path):
+    """Mask file -> (H,W,3) uint8 RGB array."""
+    return np.asarray(Image.open(fetch(path)).convert("RGB"), dtype=np.uint8).copy()
+
+
+def _colour_codes(mask_rgb):
+    m = np.asarray(mask_rgb).astype(np.int64)
+    return (m[..., 0] << 16) | (m[..., 1] << 8) | m[..., 2]
+
+
+def mask_colours(mask_rgb):
+    """The distinct colours of the content mask as sorted (r, g, b) tuples: colour k is region k.  More than MAX_REGIONS is an error."""
+    codes = np.unique(_colour_codes(mask_rgb))
+    if len(codes) > MAX_REGIONS:
+        raise ValueError(f"content mask has {len(codes)} distinct colours; at most {MAX_REGIONS} regions are supported "
+                         "(save masks without anti-aliasing or lossy compression)")
+    return [(int(c) >> 16, (int(c) >> 8) & 255, int(c) & 255) for c in codes]
+
+
+def mask_guides(mask_rgb, colours, size, what="mask"):
+    """Nearest-neighbour resize of a mask to size = (h, w) (source pixel floor(i * H / h)) and its one-hot guides: (R,h,w) float32,
+    guide k = 1 where the pixel has colours[k].  A colour that is not among `colours` is an error that names it."""
+    mask_rgb = np.asarray(mask_rgb)
+    H, W = mask_rgb.shape[:2]
+    h, w = int(size[0]), int(size[1])
+    ys = (np.arange(h, dtype=np.int64) * H) // h
+    xs = (np.arange(w, dtype=np.int64) * W) // w
+    codes = _colour_codes(mask_rgb[ys][:, xs])
+    want = np.array([(r << 16) | (g << 8) | b for r, g, b in colours], dtype=np.int64)
+    foreign = np.setdiff1d(np.unique(_colour_codes(mask_rgb)), want)
+    if len(foreign):
+        c = int(foreign[0])
+        raise ValueError(f"{what}: colour ({c >> 16}, {(c >> 8) & 255}, {c & 255}) is not a colour of the content mask")
+    return th.from_numpy((codes[None, :, :] == want[:, None, None]).astype(np.float32))
+
+
 def preprocess_video(video_path, fps=None):
     """A clip as (T,3,H,W) network-space tensor (reference load.py:35-43).  The reference decodes with skvideo at `fps`
     and falls back to a single image; here a clip is a directory of frame images (sorted by name), and a single image

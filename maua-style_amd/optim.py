@@ -21,6 +21,7 @@ import tqdm
 import config as config_mod
 import engine as engine_mod
 import hip
+import loss as loss_mod
 import plan
 import models
 from utils import limit_host_threads, wrapping_slice
@@ -37,8 +38,23 @@ def _device_image(image, args):
     return image.to(device="cuda", dtype=th.float32).contiguous()
 
 
+def _device_guide(guide, image):
+    """(R,H,W) guides of `image` (values in [0, 1], at its resolution) as a device tensor."""
+    if guide.dim() != 3 or tuple(guide.shape[1:]) != tuple(image.shape[-2:]):
+        raise ValueError(f"guides of shape {tuple(guide.shape)} for an image of {tuple(image.shape[-2:])}: expected (R, H, W) at its size")
+    return guide.to(device="cuda", dtype=th.float32).contiguous()
+
+
+def _guided(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) carry guides?  Such a network runs on the module path."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(getattr(m, "guide", None) is not None for m in mods)
+
+
 def _engine_of(net):
     """The fused engine of a loss network (built once per network; None when its module layout is not covered)."""
+    if _guided(net):
+        return None  # (not remembered: the same network without guides takes the engine again)
     eng = getattr(net, "_maua_engine", None)
     if eng is None and not getattr(net, "_maua_engine_refused", False):
         if not all(hasattr(net, a) for a in ("content_losses", "style_losses", "tv_losses", "temporal_losses")):
@@ -84,15 +100,20 @@ def set_temporal_targets(net, warp_image, warp_weights=None, args=None):
         mod.mode = "none"
 
 
-def set_style_targets(net, style_images, args):
-    """Accumulate blend-weighted Gram targets over the style images (reference optim.py:50-66)."""
+def set_style_targets(net, style_images, args, style_guides=None):
+    """Accumulate blend-weighted Gram targets over the style images (reference optim.py:50-66).  `style_guides`: one (R,H_i,W_i) guide
+    tensor per style image - each is set on the style modules before that image's capture pass (guided targets, loss.StyleLoss)."""
     _describe("Capturing style targets...", args)
+    if style_guides is not None and len(style_guides) != len(style_images):
+        raise ValueError(f"{len(style_guides)} style guides for {len(style_images)} style images")
     for mod in net.style_losses:
         mod.reset_targets()
         mod.mode = "capture"
     for i, image in enumerate(style_images):
         for mod in net.style_losses:
             mod.blend_weight = args.style_blend_weights[i]
+            if style_guides is not None:
+                mod.guide = _device_guide(style_guides[i], image)
         with th.no_grad():
             net(_device_image(image, args))
     for mod in net.style_losses:
@@ -169,6 +190,8 @@ class PixelOptimizer:
         self.independent = bool(independent) and init.shape[0] > 1
         self.grad_hook = grad_hook  # in-place edit of the gradient before the optimiser sees it (img_vid's overlap masking)
         try:
+            if _guided(losses):  # (also on the L-BFGS bundle path below: no engine, no bundle, no captured graph)
+                raise engine_mod.UnsupportedNet("guided StyleLoss runs on the module path")
             self.engine = getattr(net, "_maua_engine", None) or engine_mod.StyleEngine(net, losses)
             net._maua_engine = self.engine
         except engine_mod.UnsupportedNet:
@@ -458,10 +481,16 @@ def optimize_frames(contents, styles, inits, num_iters, args, net, losses, plann
     return opt.x.detach() if opt.owns_x else opt.x.detach().clone()
 
 
-def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep_on_device=False):
+def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep_on_device=False, guides=None):
     """Optimise `init` towards `content` / `styles`; returns a CPU fp32 tensor shaped like `init` (the reference's contract,
     optim.py:249).  Inputs may already live on the device; `keep_on_device=True` (the workflow drivers of style.py) returns
-    the device tensor instead, so that colour matching, rescaling and the next scale run without a host round trip."""
+    the device tensor instead, so that colour matching, rescaling and the next scale run without a host round trip.
+    `guides` = (content guides (R,H,W), [style guides (R,H_i,W_i) per style image]), values in [0, 1] at each image's resolution, 1 <= R
+    <= 8: spatial control - every style layer matches one Gram matrix per region (loss.StyleLoss.guide) instead of one of the whole plane.
+    One frame only, and the evaluation runs module by module (autograd over the HIP kernels), not through the fused engine."""
+    if guides is not None and ("_vid" in args.transfer_type or init.shape[0] != 1):
+        raise NotImplementedError("guides (spatial control of the style loss) are implemented for one image per call (img_img), "
+                                  "not for clips or frame batches")
     if "_vid" in args.transfer_type:
         return _optimize_video(content, styles, init, num_iters, args, net, losses, keep_on_device=keep_on_device)
     limit_host_threads()
@@ -486,16 +515,30 @@ def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep
     # (style.py:178 keeps the hoisting commented out); the result is identical, so a prebuilt net that is called again
     # with the same style tensors (vid_img: once per frame) keeps its targets.
     key = (tuple((s.data_ptr(), tuple(s.shape), s._version) for s in styles), tuple(args.style_blend_weights))
-    if getattr(net, "_maua_style_key", None) != key or any(m.target.nelement() == 0 for m in net.style_losses):
-        set_style_targets(net, styles, args)
-        net._maua_style_key = key
-        net._maua_style_refs = list(styles)  # keep the tensors alive so that data_ptr stays unique
+    if guides is not None:
+        content_guide, style_guides = guides
+        if len(net.style_losses) == 0:
+            raise ValueError("guides need at least one style layer")
+        set_style_targets(net, styles, args, style_guides=list(style_guides))
+        net._maua_style_key = None  # (guided targets: the next call captures again)
+        guide = _device_guide(content_guide, init)
+        for mod in net.style_losses:
+            mod.guide = guide
+    else:
+        if _guided(net):  # a network an earlier call guided: back to whole-plane targets
+            for mod in net.style_losses:
+                mod.guide = None
+            net._maua_style_key = None
+        if getattr(net, "_maua_style_key", None) != key or any(m.target.nelement() == 0 for m in net.style_losses):
+            set_style_targets(net, styles, args)
+            net._maua_style_key = key
+            net._maua_style_refs = list(styles)  # keep the tensors alive so that data_ptr stays unique
     for mod in losses:
         mod.mode = "loss"
 
     if args.normalize_weights:  # once per call, strengths are not reset (optim.py:176-178)
         for mod in net.content_losses + net.style_losses + net.temporal_losses:
-            mod.strength = mod.strength / max(mod.target.size())
+            mod.strength = mod.strength / loss_mod.target_dim(mod)
 
     opt = PixelOptimizer(net, losses, init, args, planned_iters=num_iters, repeated=bool(getattr(args, "_maua_repeated_calls", False)))
     _run_iterations(opt, num_iters, args)

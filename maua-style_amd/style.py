@@ -56,6 +56,24 @@ def _resize(img, size=None, scale_factor=None):
     return F.interpolate(img, scale_factor=scale_factor, mode="bilinear", align_corners=False)
 
 
+def _mask_keys(args):
+    """The file-only preset keys of the guided style loss: (content mask path, [style mask path per style image]) or None."""
+    content_mask, style_masks = getattr(args, "content_mask", None), getattr(args, "style_masks", None)
+    if content_mask is None and style_masks is None:
+        return None
+    if content_mask is None or style_masks is None:
+        raise ValueError('spatial control needs both preset keys: "content_mask" (a path) and "style_masks" (one path per style image)')
+    if isinstance(style_masks, str):
+        style_masks = [style_masks]
+    return content_mask, list(style_masks)
+
+
+def _refuse_masks(args, what):
+    if _mask_keys(args) is not None:
+        raise NotImplementedError(f'{what}: "content_mask" / "style_masks" (spatial control of the style loss) are implemented for '
+                                  "img_img only")
+
+
 def _single_rank_only(what):
     """img_img / img_vid optimise ONE image / clip (replicas only): under a multi-rank launch rank 0
     does the job and the others leave, instead of every rank redoing it on GPU 0 and racing on the output files."""
@@ -80,6 +98,12 @@ def img_img(args):
     content_image_big = match_histogram(up(load.preprocess(args.content)), style_images_big, mode=args.match_histograms)
     content_size = np.array(content_image_big.size()[-2:])
     pastiche = up(load.preprocess(args.init)) if args.init not in ("content", "random") else None
+    masks = _mask_keys(args)
+    if masks is not None:  # colour-coded region masks: the content mask's colours, sorted, are regions 0 .. R - 1
+        if len(masks[1]) != len(style_images_big):
+            raise ValueError(f"style_masks: {len(masks[1])} masks for {len(style_images_big)} style images")
+        content_mask, style_masks = load.read_mask(masks[0]), [load.read_mask(p) for p in masks[1]]
+        colours = load.mask_colours(content_mask)
 
     writer, pending = concurrent.futures.ThreadPoolExecutor(max_workers=1), []
     for current_size, num_iters in zip(args.image_sizes, args.num_iters):
@@ -102,7 +126,11 @@ def img_img(args):
             pastiche = _resize(pastiche.clone(), size=hw)
         pastiche = match_histogram(pastiche, style_images_big, mode=args.match_histograms)
 
-        output_image = optim.optimize(content_image, style_images, pastiche, num_iters, args, keep_on_device=on_gpu)
+        guides = None
+        if masks is not None:  # one-hot guides at this scale's working sizes (nearest neighbour)
+            guides = (load.mask_guides(content_mask, colours, hw, "content_mask"),
+                      [load.mask_guides(m, colours, img.shape[2:], f"style_masks[{k}]") for k, (m, img) in enumerate(zip(style_masks, style_images))])
+        output_image = optim.optimize(content_image, style_images, pastiche, num_iters, args, keep_on_device=on_gpu, guides=guides)
 
         pastiche = match_histogram(output_image.detach(), style_images_big, mode=args.match_histograms)
         # deprocessing = one kernel + a 3-byte-per-pixel download, here; PNG encoding (host only) runs beside the next scale
@@ -122,6 +150,7 @@ def img_vid(args):
     of frame images on both sides (no codecs in this build): style clips are read with load.preprocess_video, each
     scale's result goes to <output>_<size>/frame_#####.png and the final clip to <output>/."""
     import scipy.ndimage as ndi
+    _refuse_masks(args, "img_vid")
     if not _single_rank_only("img_vid"):
         return None
     limit_host_threads()
@@ -574,6 +603,7 @@ def vid_img(args):
     convolutions of a batch run together, each frame keeps its own losses and optimiser state, results are bit-identical to
     the frame-by-frame loop.  Frames stay on the device from decoding to the 8-bit image; the global RNG is drawn from in the
     frame-by-frame order (colour-matching jitter, random initialisation)."""
+    _refuse_masks(args, "vid_img")
     limit_host_threads()
     rank, _, world = dist.init()
     output_dir = args.output_dir + "/" + name(args.content) + "_" + "_".join([name(s) for s in args.style])

@@ -48,7 +48,8 @@ def main():
                  L.maua_conv_kxk_x3_bank_bytes(cout, cin, k), L.maua_gram_workspace_bytes(cin, h * w if abs(h * w) < 1 << 40 else 1),
                  L.maua_reduce_workspace_bytes(h * w), L.maua_lbfgs_state_bytes(h * w, rng.choice([1, 5, 100, 254, 255, 0, -1])),
                  L.maua_channel_stats_workspace_bytes(h, w), L.maua_loss_ledger_bytes(n, cin),
-                 L.maua_conv_image_bank_bytes(cout, cin), L.maua_flow_warp_grid_workspace_bytes(h, w)]
+                 L.maua_conv_image_bank_bytes(cout, cin), L.maua_flow_warp_grid_workspace_bytes(h, w),
+                 L.maua_gram_guided_workspace_bytes(rng.choice([1, 2, 8, 0, 9, -1]), cin, h * w if abs(h * w) < 1 << 40 else 1)]
         assert all(s >= 0 for s in sizes)
         if min(n, cin, cout, h, w) <= 0:
             assert sizes[1] == 0 and sizes[2] == 0 and sizes[3] == 0, (n, cin, cout, h, w, sizes)
@@ -96,6 +97,12 @@ def main():
             L.maua_conv_pack_dmat_x3w_batch(rng.choice([0, -1, 5, 1000]), None, None, None, None, None),
             L.maua_gram_finish_mse_batch(rng.choice([0, -1, 9, 1000]), None, None, None, None, None, None, None, None, None, None, None, None, None),
             L.maua_gram_mse_ledger_supported(cin),
+            L.maua_gram_guided_supported(rng.choice([1, 8, 0, 9, -1]), cin, h * w if abs(h * w) < 1 << 40 else 1),
+            L.maua_gram_guided_mass(ptr, ptr, rng.choice([1, 3, 8, 0, 9, -1]), h * w if abs(h * w) < 1 << 40 else 1, None),
+            L.maua_gram_guided_fwd(ptr, ptr, ptr, ptr, ptr, ptr, rng.choice([1, 3, 8, 0, 9, -1]), cin, h * w if abs(h * w) < 1 << 40 else 1, case % 2,
+                                   ptr, ws_bytes, None),
+            L.maua_gram_guided_bwd(ptr, ptr, ptr, ptr, rng.choice([None, ptr]), ptr, rng.choice([1, 3, 8, 0, 9, -1]), cin,
+                                   h * w if abs(h * w) < 1 << 40 else 1, case % 2, None),
             L.maua_tv_fwd_bwd(ptr, ptr, n, cin, h, w, 1.0, 0, ptr, ptr, ws_bytes, None),
             L.maua_resize_bilinear(ptr, ptr, n, h, w, cout, cin, 0.5, 0.5, None),
             L.maua_channel_stats(ptr, None, 1e-3, n, rng.randint(-1, 3), h, w, ptr, ptr, ws_bytes, None),
