@@ -348,6 +348,31 @@ int maua_gram_guided_fwd(const float* f, const float* guides, const float* scale
                          int regions, int c, int64_t hw, int center, void* workspace, size_t workspace_bytes, maua_stream_t stream);
 int maua_gram_guided_bwd(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean, float* gf, int regions,
                          int c, int64_t hw, int accumulate, maua_stream_t stream);
+/* The guided layer of the fused engine: the forward pass with the MSE against per-region targets formed by its finishing launch, and the
+ * backward pass with a ReLU mask in its epilogue.
+ * maua_guided_gram_fwd_mse_ledger: maua_gram_guided_fwd (gram and mean_out: the same bits - same slabs, same fixed-order fp64 fold, same
+ *   mirror) whose finishing launch also writes
+ *     dmat[r][C][C] = grad_scale[r] * (gram[r] - target[r]), formed on the upper triangle and mirrored like gram[r] (exactly symmetric; the
+ *       target is read on and above its diagonal only); exact zeros - written, never left out - where scale[r] == 0 or grad_scale[r] == 0;
+ *     ONE ledger record for the layer in `slot` of `ledger` (maua_loss_ledger_bytes): sum_r loss_scale[r] * sum (gram[r] - target[r])^2
+ *       (gram[r] = 0 for an inactive region), every partial sum weighted by its region's loss_scale, the record's scale 1; a region with
+ *       loss_scale[r] == 0 contributes exact zeros and its target is not read for the loss.
+ *   target[regions][C][C]; loss_scale[regions], grad_scale[regions]: device floats like scale.  Deterministic: no float atomics, the same
+ *   inputs give the same bits.  workspace: maua_gram_guided_workspace_bytes, as for maua_gram_guided_fwd.
+ * maua_guided_gram_mse_ledger_supported: 1 when the finishing launch's partial sums - 16, 8 or 4 per (region, 64 x 64 tile pair of the
+ *   upper triangle): the most that fit, a function of (regions, C) alone - fit one record:  regions * nt (nt + 1) / 2 * 4 <= 4096,
+ *   nt = ceil(C / 64)  (8 regions: C <= 960, 1 region: C <= 2816; VGG-19's 8 x 512 takes 8 per pair, 2304).  Other shapes: maua_guided_gram_fwd_mse_ledger returns MAUA_E_UNSUPPORTED before any launch, as do the
+ *   argument checks of maua_gram_guided_fwd.
+ * maua_guided_gram_bwd_masked: maua_gram_guided_bwd with relu_mask[C][hw] (nullable): where relu_mask <= 0 the element of gf is written
+ *   as 0 (also with accumulate != 0: what was accumulated into is dropped - pre-masked gradients, as maua_gram_bwd's relu_mask).  A null
+ *   mask gives the bits of maua_gram_guided_bwd.  One launch, the mask is applied in its epilogue. */
+int maua_guided_gram_mse_ledger_supported(int regions, int c);
+int maua_guided_gram_fwd_mse_ledger(const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
+                                    int regions, int c, int64_t hw, int center, const float* target, const float* loss_scale,
+                                    const float* grad_scale, float* dmat, double* ledger, int slot, void* workspace, size_t workspace_bytes,
+                                    maua_stream_t stream);
+int maua_guided_gram_bwd_masked(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean,
+                                const float* relu_mask, float* gf, int regions, int c, int64_t hw, int accumulate, maua_stream_t stream);
 
 /* ---- total variation: loss.TVLoss.forward, loss.py:224-233, and its autograd ---------------------- */
 /* loss_out[0] = strength * (sum|dy| + sum|dx|); grad (+)= strength * d/dx.  workspace as for the MSE. */

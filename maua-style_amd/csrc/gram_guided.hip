@@ -11,6 +11,8 @@
 // Backward: gram_bwd_kernel's layout (64 output channels x 256 pixels per workgroup, F staged with 16-byte loads in its own order); the
 // regions are further stages of the same accumulation, each staged as coef_r g_r^2 (F - mu_r) against D_r, and a region whose guide is
 // zero over the workgroup's 256 pixels (or whose coef_r is 0) is left out.
+// For the fused engine: a finishing kernel that also forms D_r = grad_scale_r (G_r - T_r) and the layer's loss as one ledger record
+// (gg_finish_mse_kernel), and a ReLU mask in the backward kernel's epilogue (gg_bwd_kernel's MASK flag).
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
@@ -244,14 +246,111 @@ gg_finish_kernel(const float* __restrict__ partial, const float* __restrict__ sc
     }
 }
 
+// gg_finish_kernel and the MSE against the regions' targets in one launch: grid (tile pairs, 16 / FQ, R), every thread owns FQ elements of
+// the 64x64 tile (e = 256 (FQ blockIdx.y + u) + tid).  Each element's slab values are added in index order in fp64 exactly as
+// gg_finish_kernel adds them (the same bits); the loads of the thread's FQ elements for eight slabs are requested together.
+// D_r = grad_scale_r (G_r - T_r) is formed once per element of the upper triangle and written with its mirror (exactly symmetric whatever
+// the target holds below its diagonal); exact zeros for a region with scale_r == 0 or grad_scale_r == 0.  The workgroup's share of
+// loss_scale_r sum (G_r - T_r)^2 - off-diagonal tiles count twice - is one partial sum of the layer's ledger record (scale 1): R x pairs
+// x 16 / FQ partial sums, a fixed order, no atomics.  The host takes the smallest FQ of 1, 2, 4 whose partial sums fit the record
+// (gg_finish_split): FQ = 1 is gg_finish_kernel's grid - the serial chain of a thread is its slabs, so fewer, longer threads are slower
+// where a layer has few tile pairs and many slabs - and FQ = 4 holds eight regions of 512 channels (8 x 36 x 4 sums).
+constexpr int GG_FQ_MAX = 4;  // most elements per thread: 16 / 4 workgroups per (region, tile pair)
+template <int FQ>
+__global__ void __launch_bounds__(256)
+gg_finish_mse_kernel(const float* __restrict__ partial, const float* __restrict__ scale, float* __restrict__ gram, int C, int npairs, int ksplit,
+                     const float* __restrict__ target, const float* __restrict__ loss_scale, const float* __restrict__ grad_scale,
+                     float* __restrict__ dmat, double* __restrict__ rec) {
+    constexpr int GG_FQ = FQ;
+    __shared__ double scratch[16];
+    const int reg = blockIdx.z;
+    int pair = blockIdx.x, ti = 0;
+    const int ntile = (C + GG_T - 1) / GG_T;
+    while (pair >= ntile - ti) {
+        pair -= ntile - ti;
+        ++ti;
+    }
+    const int tj = ti + pair;
+    const float sc = scale[reg], ls = loss_scale[reg], gs = grad_scale[reg];
+    int er[GG_FQ], ec[GG_FQ], src[GG_FQ];
+#pragma unroll
+    for (int u = 0; u < GG_FQ; ++u) {
+        const int e = (blockIdx.y * GG_FQ + u) * 256 + threadIdx.x;
+        er[u] = e / GG_T;
+        ec[u] = e % GG_T;
+        src[u] = (ti == tj && er[u] > ec[u]) ? ec[u] * GG_T + er[u] : e;
+    }
+    float s[GG_FQ];
+#pragma unroll
+    for (int u = 0; u < GG_FQ; ++u) s[u] = 0.f;
+    if (sc != 0.f) {
+        const float* base = partial + ((int64_t)reg * npairs + blockIdx.x) * ksplit * (GG_T * GG_T);
+        double sd[GG_FQ];
+#pragma unroll
+        for (int u = 0; u < GG_FQ; ++u) sd[u] = 0.0;
+        int k = 0;
+        for (; k + 7 < ksplit; k += 8) {  // 8 GG_FQ loads in flight, each element's additions in the order of a plain loop
+            float v[GG_FQ][8];
+#pragma unroll
+            for (int u = 0; u < GG_FQ; ++u)
+#pragma unroll
+                for (int w = 0; w < 8; ++w) v[u][w] = base[(int64_t)(k + w) * (GG_T * GG_T) + src[u]];
+#pragma unroll
+            for (int u = 0; u < GG_FQ; ++u)
+#pragma unroll
+                for (int w = 0; w < 8; ++w) sd[u] += (double)v[u][w];
+        }
+        for (; k < ksplit; ++k) {
+            float v[GG_FQ];
+#pragma unroll
+            for (int u = 0; u < GG_FQ; ++u) v[u] = base[(int64_t)k * (GG_T * GG_T) + src[u]];
+#pragma unroll
+            for (int u = 0; u < GG_FQ; ++u) sd[u] += (double)v[u];
+        }
+#pragma unroll
+        for (int u = 0; u < GG_FQ; ++u) s[u] = (float)(sd[u] * (double)sc);
+    }
+    const bool with_d = sc != 0.f && gs != 0.f;
+    const int64_t mat = (int64_t)reg * C * C;
+    double sq = 0.0;
+#pragma unroll
+    for (int u = 0; u < GG_FQ; ++u) {
+        const int gi = ti * GG_T + er[u], gj = tj * GG_T + ec[u];
+        if (gi < C && gj < C) {
+            // the element of the upper triangle this one mirrors (itself unless it lies below the diagonal of a diagonal tile)
+            const bool low = ti == tj && er[u] > ec[u];
+            const int64_t up = low ? (int64_t)gj * C + gi : (int64_t)gi * C + gj;
+            float d = 0.f;
+            if (with_d || ls != 0.f) d = s[u] - target[mat + up];
+            const float dv = with_d ? gs * d : 0.f;
+            gram[mat + (int64_t)gi * C + gj] = s[u];
+            dmat[mat + (int64_t)gi * C + gj] = dv;
+            if (ti != tj) {
+                gram[mat + (int64_t)gj * C + gi] = s[u];
+                dmat[mat + (int64_t)gj * C + gi] = dv;
+            }
+            if (ls != 0.f) sq += (ti != tj ? 2.0 : 1.0) * ((double)d * (double)d);
+        }
+    }
+    sq = block_sum(sq, scratch);
+    if (threadIdx.x == 0) {
+        rec[2 + ((int64_t)reg * npairs + blockIdx.x) * gridDim.y + blockIdx.y] = sq * (double)ls;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && reg == 0) {
+            rec[0] = (double)(gridDim.x * gridDim.y * gridDim.z);
+            rec[1] = 1.0;
+        }
+    }
+}
+
 // Backward.  Workgroup = 64 output channels x 256 pixels, wave = 64 x 64 (2 x 2 accumulators), 32 input channels per LDS stage,
 // double-buffered (80 KB); the stages run over (active region, channel block).
 constexpr int GGB_KC = 32, GGB_PX = 256, GGB_CO = 64;
 
-template <bool ACC>
+// MASK: the sums (and what they were accumulated into) are written as 0 where relu_mask[c][p] <= 0 (gram_bwd_kernel's pre-masked gradients).
+template <bool ACC, bool MASK>
 __global__ void __launch_bounds__(256)
 gg_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ guides, const float* __restrict__ coef,
-              const float* __restrict__ mean, float* __restrict__ gf, int R, int C, int64_t HW) {
+              const float* __restrict__ mean, const float* __restrict__ relu_mask, float* __restrict__ gf, int R, int C, int64_t HW) {
     extern __shared__ __attribute__((aligned(16))) float smem_f32[];  // 2 x (Xl[32][256] + Wl[32][64])
     float* smem = smem_f32;
     constexpr int BUF = GGB_KC * GGB_PX + GGB_KC * GGB_CO;
@@ -366,19 +465,23 @@ gg_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             // read-modify-write in two sweeps: all loads of the 16 registers first, then all stores (gram_bwd_kernel)
-            float prev[16];
+            float prev[16], mk[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
                 const bool ok = pix < HW && co < C;
                 const int64_t o = ok ? (int64_t)co * HW + pix : 0;
                 prev[q] = 0.f;
+                mk[q] = 1.f;
                 if constexpr (ACC) prev[q] = gf[o];
+                if constexpr (MASK) mk[q] = relu_mask[o];
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
-                if (pix < HW && co < C) gf[(int64_t)co * HW + pix] = acc[t][u][q] + prev[q];
+                float v = acc[t][u][q] + prev[q];
+                if constexpr (MASK) v = mk[q] <= 0.f ? 0.f : v;
+                if (pix < HW && co < C) gf[(int64_t)co * HW + pix] = v;
             }
         }
     }
@@ -396,6 +499,14 @@ static void gg_plan(int c, int64_t hw, int* npairs, int* ksplit, int64_t* chunk)
     const int64_t ch = ((hw + want - 1) / want + GG_K - 1) / GG_K * GG_K;
     *chunk = ch;
     *ksplit = (int)((hw + ch - 1) / ch);
+}
+
+// elements per thread of gg_finish_mse_kernel: the smallest of 1, 2, 4 for which regions x pairs x 16 / FQ partial sums fit one ledger record
+// (0: not even GG_FQ_MAX does)
+static int gg_finish_split(int regions, int64_t npairs) {
+    for (int fq = 1; fq <= GG_FQ_MAX; fq *= 2)
+        if ((int64_t)regions * npairs * (GG_T * GG_T / 256 / fq) <= LEDGER_MAX) return fq;
+    return 0;
 }
 
 static bool gg_shape_ok(int regions, int c, int64_t hw) {
@@ -428,14 +539,23 @@ int maua_gram_guided_mass(const float* guides, double* mass, int regions, int64_
     return check_launch("gg_mass_kernel");
 }
 
-int maua_gram_guided_fwd(const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
-                         int regions, int c, int64_t hw, int center, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
-    MAUA_REQUIRE(f && guides && scale && gram && workspace, MAUA_E_INVAL, "gram_guided_fwd: null pointer");
-    MAUA_REQUIRE(!center || (mass && mean_out), MAUA_E_INVAL, "gram_guided_fwd: center needs mass and mean_out");
-    MAUA_REQUIRE(gg_shape_ok(regions, c, hw), MAUA_E_UNSUPPORTED, "gram_guided_fwd: %d regions (1 .. %d), %d channels, %lld pixels", regions,
-                 GG_RMAX, c, (long long)hw);
+// maua_gram_guided_fwd; with `mse` the finishing launch is gg_finish_mse_kernel
+struct GuidedMse {
+    const float *target, *loss_scale, *grad_scale;
+    float* dmat;
+    double* rec;
+};
+static int gg_forward(const char* who, const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
+                      int regions, int c, int64_t hw, int center, void* workspace, size_t workspace_bytes, const GuidedMse* mse,
+                      maua_stream_t stream) {
+    MAUA_REQUIRE(f && guides && scale && gram && workspace, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(!center || (mass && mean_out), MAUA_E_INVAL, "%s: center needs mass and mean_out", who);
+    MAUA_REQUIRE(gg_shape_ok(regions, c, hw), MAUA_E_UNSUPPORTED, "%s: %d regions (1 .. %d), %d channels, %lld pixels", who, regions, GG_RMAX, c,
+                 (long long)hw);
+    MAUA_REQUIRE(!mse || maua_guided_gram_mse_ledger_supported(regions, c), MAUA_E_UNSUPPORTED,
+                 "%s: %d regions of %d channels need more than %d partial sums", who, regions, c, LEDGER_MAX);
     const size_t need = maua_gram_guided_workspace_bytes(regions, c, hw);
-    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "gram_guided_fwd: workspace %zu < %zu", workspace_bytes, need);
+    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
     int npairs, ksplit;
     int64_t chunk;
     gg_plan(c, hw, &npairs, &ksplit, &chunk);
@@ -454,25 +574,73 @@ int maua_gram_guided_fwd(const float* f, const float* guides, const float* scale
                        (float*)workspace, c, hw, npairs, ksplit, chunk);
     int rc = check_launch("gg_partial_kernel");
     if (rc) return rc;
+    if (mse) {
+        const int fq = gg_finish_split(regions, npairs);
+        auto finish = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(npairs, GG_T * GG_T / 256 / fq, regions), dim3(256), 0, s, (const float*)workspace, scale, gram, c, npairs,
+                               ksplit, mse->target, mse->loss_scale, mse->grad_scale, mse->dmat, mse->rec);
+        };
+        if (fq == 1) finish(gg_finish_mse_kernel<1>);
+        else if (fq == 2) finish(gg_finish_mse_kernel<2>);
+        else finish(gg_finish_mse_kernel<4>);
+        return check_launch("gg_finish_mse_kernel");
+    }
     hipLaunchKernelGGL(gg_finish_kernel, dim3(npairs, GG_T * GG_T / 256, regions), dim3(256), 0, s, (const float*)workspace, scale, gram, c, npairs,
                        ksplit);
     return check_launch("gg_finish_kernel");
 }
 
-int maua_gram_guided_bwd(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean, float* gf, int regions,
-                         int c, int64_t hw, int accumulate, maua_stream_t stream) {
-    MAUA_REQUIRE(d_sym && f && guides && coef && gf, MAUA_E_INVAL, "gram_guided_bwd: null pointer");
-    MAUA_REQUIRE(gg_shape_ok(regions, c, hw), MAUA_E_UNSUPPORTED, "gram_guided_bwd: %d regions (1 .. %d), %d channels, %lld pixels", regions,
-                 GG_RMAX, c, (long long)hw);
+int maua_gram_guided_fwd(const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
+                         int regions, int c, int64_t hw, int center, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    return gg_forward("gram_guided_fwd", f, guides, scale, mass, gram, mean_out, regions, c, hw, center, workspace, workspace_bytes, nullptr, stream);
+}
+
+int maua_guided_gram_mse_ledger_supported(int regions, int c) {
+    if (!gg_shape_ok(regions, c, 1)) return 0;
+    const int64_t nt = (c + GG_T - 1) / GG_T;
+    return gg_finish_split(regions, nt * (nt + 1) / 2) != 0 ? 1 : 0;
+}
+
+int maua_guided_gram_fwd_mse_ledger(const float* f, const float* guides, const float* scale, const double* mass, float* gram, float* mean_out,
+                                    int regions, int c, int64_t hw, int center, const float* target, const float* loss_scale,
+                                    const float* grad_scale, float* dmat, double* ledger, int slot, void* workspace, size_t workspace_bytes,
+                                    maua_stream_t stream) {
+    MAUA_REQUIRE(target && loss_scale && grad_scale && dmat && ledger && slot >= 0 && slot < (1 << 28), MAUA_E_INVAL,
+                 "guided_gram_fwd_mse_ledger: bad args");
+    const GuidedMse m{target, loss_scale, grad_scale, dmat, ledger + (int64_t)slot * LEDGER_STRIDE};
+    return gg_forward("guided_gram_fwd_mse_ledger", f, guides, scale, mass, gram, mean_out, regions, c, hw, center, workspace, workspace_bytes, &m,
+                      stream);
+}
+
+static int gg_backward(const char* who, const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean,
+                       const float* relu_mask, float* gf, int regions, int c, int64_t hw, int accumulate, maua_stream_t stream) {
+    MAUA_REQUIRE(d_sym && f && guides && coef && gf, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(gg_shape_ok(regions, c, hw), MAUA_E_UNSUPPORTED, "%s: %d regions (1 .. %d), %d channels, %lld pixels", who, regions, GG_RMAX, c,
+                 (long long)hw);
     constexpr size_t lds = 2ull * (GGB_KC * GGB_PX + GGB_KC * GGB_CO) * sizeof(float);
     const dim3 grid((unsigned)((hw + GGB_PX - 1) / GGB_PX), (unsigned)((c + GGB_CO - 1) / GGB_CO));
     auto launch = [&](auto kernel) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d_sym, f, guides, coef, mean, gf, regions, c, hw);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d_sym, f, guides, coef, mean, relu_mask, gf, regions, c, hw);
     };
-    if (accumulate) launch(gg_bwd_kernel<true>);
-    else launch(gg_bwd_kernel<false>);
+    if (relu_mask) {
+        if (accumulate) launch(gg_bwd_kernel<true, true>);
+        else launch(gg_bwd_kernel<false, true>);
+    } else {
+        if (accumulate) launch(gg_bwd_kernel<true, false>);
+        else launch(gg_bwd_kernel<false, false>);
+    }
     return check_launch("gg_bwd_kernel");
+}
+
+int maua_gram_guided_bwd(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean, float* gf, int regions,
+                         int c, int64_t hw, int accumulate, maua_stream_t stream) {
+    return gg_backward("gram_guided_bwd", d_sym, f, guides, coef, mean, nullptr, gf, regions, c, hw, accumulate, stream);
+}
+
+int maua_guided_gram_bwd_masked(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean,
+                                const float* relu_mask, float* gf, int regions, int c, int64_t hw, int accumulate, maua_stream_t stream) {
+    return gg_backward("guided_gram_bwd_masked", d_sym, f, guides, coef, mean, relu_mask, gf, regions, c, hw, accumulate, stream);
 }
 
 }  // extern "C"

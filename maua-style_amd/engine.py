@@ -39,6 +39,24 @@ def _scale_grad_coeff(incoming, strength):
     return g / (abs(g) + 1e-8) * strength * strength
 
 
+def guided_coefficients(strength, video_style_factor, normalize, channels, active, has_target):
+    """Per-region (loss_scale [R], grad_scale [R]) of a guided StyleLoss for hip.gram_guided_fwd_mse_ledger - what loss.StyleLoss.guided_loss
+    and loss._GuidedGramFn do for one frame: region r contributes iff active[r] and has_target[r]; its t_r = mean((G_r - T_r)^2) enters the
+    loss with lw = s + (vsf * s if vsf > 0) and the gradient with gw = lw, or through ScaleGradients (sign * s^2 per term) with `normalize`.
+    loss_scale[r] = lw / C^2; grad_scale[r] = gw * 4 / C^2 scales G_r - T_r into dG_r + dG_r^T, the matrix of the backward kernel (whose
+    1 / (C N_r) is its coef = LayerGuides.scale).  Pure host arithmetic."""
+    s, vsf = strength, video_style_factor
+    dyn = vsf > 0
+    lw = s + (vsf * s if dyn else 0.0)
+    if normalize:
+        gw = _scale_grad_coeff(s, s) + (_scale_grad_coeff(vsf * s, s) if dyn else 0.0)
+    else:
+        gw = lw
+    cc = float(channels) * float(channels)
+    on = [bool(a) and bool(h) for a, h in zip(active, has_target)]
+    return [lw / cc if o else 0.0 for o in on], [gw * 4.0 / cc if o else 0.0 for o in on]
+
+
 class _Step:
     __slots__ = ("kind", "mod", "relu", "src", "dst", "slot", "k", "stride", "pad", "ceil", "mode")
 
@@ -82,7 +100,7 @@ class StyleEngine:
                 s = _Step("content", m)
                 s.src = act
             elif isinstance(m, loss_mod.StyleLoss):
-                if getattr(m, "guide", None) is not None:
+                if getattr(m, "guide", None) is not None and not plan.on("guided_engine"):
                     raise UnsupportedNet("guided StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
@@ -126,12 +144,22 @@ class StyleEngine:
     # -- buffers ---------------------------------------------------------------------------------------
     def _prepare(self, x):
         hip.set_split_batch_hint(self.batch_hint)
-        if self.shape == tuple(x.shape) and getattr(self, "prepared_for", None) == (self.independent, self.batch_hint):
+        # planner field guided_engine: a style step whose module carries guides is planned as a guided step (per-region Gram matrices, none of
+        # the whole-plane fusions below); which steps are guided, and with how many regions, is part of what the plan was made for
+        regions = {id(s): s.mod.guide.shape[0] for s in self.steps if s.kind == "style" and getattr(s.mod, "guide", None) is not None} \
+            if plan.on("guided_engine") else {}
+        made_for = (self.independent, self.batch_hint) + ((tuple(regions.get(id(s)) for s in self.steps if s.kind == "style"),) if regions else ())
+        if self.shape == tuple(x.shape) and getattr(self, "prepared_for", None) == made_for:
+            self._refresh_guided()
             return
         dev = x.device
         B = x.shape[0]
+        if regions and (B != 1 or self.independent):
+            raise UnsupportedNet("guided StyleLoss on the engine: one frame per evaluation (B = 1)")
+        if regions and not plan.on("loss_ledger"):
+            raise UnsupportedNet("guided StyleLoss on the engine needs the loss ledger (planner field loss_ledger)")
         self.shape = tuple(x.shape)
-        self.prepared_for = (self.independent, self.batch_hint)
+        self.prepared_for = made_for
         self.graph = None
         self.alloc_epoch = getattr(self, "alloc_epoch", 0) + 1  # every buffer below is new: graphs captured over the old ones are void
         self.iter_graphs = {}
@@ -143,6 +171,10 @@ class StyleEngine:
                 shapes[s.dst] = (n, s.mod.out_channels, oh, ow)
             elif s.kind == "pool":
                 shapes[s.dst] = (n, c, hip.pool_out_size(h, s.k, s.stride, s.ceil), hip.pool_out_size(w, s.k, s.stride, s.ceil))
+        for s in self.steps:
+            if id(s) in regions and not hip.gram_guided_mse_ledger_supported(regions[id(s)], shapes[s.src][1]):
+                self.shape = None  # (no plan was made)
+                raise UnsupportedNet(f"guided StyleLoss: {regions[id(s)]} regions of {shapes[s.src][1]} channels do not fit one ledger record")
         self.act = {k: (None if k == 0 else torch.empty(v, device=dev)) for k, v in shapes.items()}
         self.gbuf = {k: torch.empty(v, device=dev) for k, v in shapes.items()}
         # 2x2/2 max pools on even planes keep their decisions (one byte per window) for the backward pass
@@ -228,7 +260,7 @@ class StyleEngine:
                     continue
                 on_src = [t for t in self.steps if t.kind in ("style", "content") and t.src == s.src]
                 c, h, w = shapes[s.src][1:]
-                if len(on_src) == 1 and on_src[0].kind == "style" and not on_src[0].mod.use_covariance and c % 16 == 0 and \
+                if len(on_src) == 1 and on_src[0].kind == "style" and id(on_src[0]) not in regions and not on_src[0].mod.use_covariance and c % 16 == 0 and \
                         c <= max_c and self._x6_ok(s, s.mod.in_channels) and models_mod.conv3x3_bwd_is_x3w(s.mod, *shapes[s.dst][2:]):
                     bank = hip.conv_x3w_dmat_bank(c, dev, B)
                     if bank is not None:
@@ -246,7 +278,7 @@ class StyleEngine:
                         not self._x6_ok(s, 64):
                     continue
                 on_dst = [t for t in self.steps if t.kind == "style" and t.src == s.dst]
-                if len(on_dst) == 1 and not on_dst[0].mod.use_covariance and hip.gram_mse_ledger_supported(64):
+                if len(on_dst) == 1 and id(on_dst[0]) not in regions and not on_dst[0].mod.use_covariance and hip.gram_mse_ledger_supported(64):
                     h, w = shapes[s.src][2:]
                     slabs = hip.conv_image_gram_slabs(h, w, s.pad)
                     if 0 < slabs * 64 * 64 * 4 <= hip.gram_workspace_bytes(64, shapes[s.dst][2] * shapes[s.dst][3]):
@@ -254,8 +286,20 @@ class StyleEngine:
         self.gram, self.dmat, self.mean = {}, {}, {}
         self.gram_d, self.dmat_d, self.mean_d = {}, {}, {}
         ws = hip.reduce_workspace_bytes(max(t.numel() for t in self.gbuf.values()))
+        # guided steps: one matrix per region; the layer guides and targets are looked up by _refresh_guided (a host read-back or a print the
+        # first time: outside any capture), the two coefficient arrays keep their addresses and get new values when a strength changes
+        self.guided = {}
         for s in self.steps:
-            if s.kind == "style":
+            if id(s) in regions:
+                r, c = regions[id(s)], shapes[s.src][1]
+                hw = shapes[s.src][2] * shapes[s.src][3]
+                self.gram[id(s)], self.dmat[id(s)] = torch.empty(r, c, c, device=dev), torch.empty(r, c, c, device=dev)
+                self.mean[id(s)] = torch.empty(r, c, device=dev) if s.mod.use_covariance else None
+                self.guided[id(s)] = dict(loss_scale=torch.zeros(r, device=dev), grad_scale=torch.zeros(r, device=dev), coef=None, lg=None,
+                                          target=None, chw=(c, shapes[s.src][2], shapes[s.src][3]))
+                ws = max(ws, hip.gram_guided_workspace_bytes(r, c, hw))
+        for s in self.steps:
+            if s.kind == "style" and id(s) not in regions:
                 c = shapes[s.src][1]
                 hw = shapes[s.src][2] * shapes[s.src][3]
                 self.gram[id(s)] = torch.empty(B, c, c, device=dev) if B > 1 else torch.empty(c, c, device=dev)
@@ -308,7 +352,8 @@ class StyleEngine:
         self.x_static = torch.empty(self.shape, device=dev)
         if plan.get("debug_poison") == "1":  # tests: every buffer starts as NaN, so a read-before-write shows up
             for t in list(self.act.values()) + list(self.gbuf.values()) + list(self.gram.values()) + list(self.dmat.values()) + \
-                    list(self.gram_d.values()) + list(self.dmat_d.values()):
+                    list(self.gram_d.values()) + list(self.dmat_d.values()) + [self.mean[k] for k in self.guided] + \
+                    [t for gd in self.guided.values() for t in (gd["loss_scale"], gd["grad_scale"])]:
                 if t is not None and not t.is_meta:
                     t.fill_(float("nan"))
             self.ws[:self.ws.numel() // 4 * 4].view(torch.float32)[:] = float("nan")
@@ -339,6 +384,27 @@ class StyleEngine:
             self.side_ws = [torch.empty(small, dtype=torch.uint8, device=dev) for _ in range(ns)]
             self.ev_main = torch.cuda.Event()
             self.ev_side = [torch.cuda.Event() for _ in range(ns)]
+        self._refresh_guided()
+
+    def _refresh_guided(self):
+        """Guided steps (every _prepare, so never inside a capture): the module's layer guides and targets as they are now - both cached on
+        the module, their first look-up reads the masses back / names regions without a target - and the coefficient arrays, rewritten
+        in place when a strength, a region's activity or its target changed.  _graph_key covers all of them."""
+        for s in self.steps:
+            gd = getattr(self, "guided", {}).get(id(s))
+            if gd is None:
+                continue
+            m = s.mod
+            c = gd["chw"][0]
+            gd["lg"] = lg = m.layer_guides(*gd["chw"])
+            ok = m.guided_target is not None and tuple(m.guided_target.shape) == (lg.g.shape[0], c, c)
+            gd["target"], has = m.guided_targets() if ok else (None, [False] * lg.g.shape[0])
+            coef = guided_coefficients(m.strength, m.video_style_factor, m.normalize, c, lg.active, has)
+            coef = (tuple(coef[0]), tuple(coef[1]))
+            if coef != gd["coef"]:
+                gd["loss_scale"].copy_(torch.tensor(coef[0], dtype=torch.float64).float())
+                gd["grad_scale"].copy_(torch.tensor(coef[1], dtype=torch.float64).float())
+                gd["coef"] = coef
 
     # -- one evaluation --------------------------------------------------------------------------------
     def _style_terms(self, s, B):
@@ -393,8 +459,15 @@ class StyleEngine:
                         or w.shape[1] not in (1, shapes_src[1]):
                     raise UnsupportedNet("weighted ContentLoss of this shape runs on the module path")
             return True
-        if getattr(m, "guide", None) is not None:  # (guides set after the plan was made)
-            raise UnsupportedNet("guided StyleLoss runs on the module path")
+        if getattr(m, "guide", None) is not None:
+            gd = getattr(self, "guided", {}).get(id(s)) if plan.on("guided_engine") else None
+            if gd is None:  # (planner field guided_engine off, or guides set after the plan was made)
+                raise UnsupportedNet("guided StyleLoss runs on the module path")
+            if gd["target"] is None:
+                if m.guided_target is None:
+                    raise RuntimeError(f"{getattr(m, 'name', 'StyleLoss')}: guided style target not captured")
+                raise ValueError("guided StyleLoss: content and style guides must name the same regions")
+            return True
         if m.target.nelement() == 0:
             raise RuntimeError(f"{m.name}: style target not captured")
         if shapes_src[0] == 1 and m.video_style_factor > 0 and m.video_target.nelement() != 0 \
@@ -531,6 +604,16 @@ class StyleEngine:
                     hip.pool2x2_fwd_codes(a[s.src], a[s.dst], self.pool_codes[id(s)])
                 else:
                     hip.pool2d_fwd(a[s.src], s.k, s.stride, s.ceil, s.mode, out=a[s.dst])
+            elif s.kind == "style" and id(s) in self.guided:
+                if self._active(s, a[s.src].shape):
+                    # one Gram matrix per region; the finishing launch leaves every region's D = grad_scale_r (G_r - T_r) and the layer's
+                    # loss as ONE ledger record (csrc/gram_guided.hip) - on this stream, its own launches, no whole-plane fusion
+                    f, gd = a[s.src], self.guided[id(s)]
+                    lg, cov = gd["lg"], bool(s.mod.use_covariance)
+                    c, n, r = f.shape[1], f[0].nelement(), gd["lg"].g.shape[0]
+                    self._timed("gram_fwd", 2 * c * c * (n // c), n * 4 + r * c * c * 4, lambda: hip.gram_guided_fwd_mse_ledger(
+                        f, lg.g, lg.scale, cov, lg.mass, self.gram[id(s)], self.mean[id(s)], gd["target"], self.dmat[id(s)], gd["loss_scale"],
+                        gd["grad_scale"], self.ledger[0], s.slot, workspace=self.ws))
             elif s.kind == "style" and self.independent and a[s.src].shape[0] > 1 and self._active(s, a[s.src].shape):
                 f = a[s.src]
                 c, n = f.shape[1], f[0].nelement()
@@ -764,8 +847,13 @@ class StyleEngine:
                     c, n = f.shape[1], f[0].nelement()
                     acc = cur == s.src
                     rm = f if premask(s) else None
-                    self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + c * c * 4, lambda: hip.gram_bwd(
-                        self.dmat[id(s)], f, self.mean[id(s)], g[s.src], acc, workspace=self.ws, relu_mask=rm))
+                    if id(s) in self.guided:  # every region's D_r (F - mu_r) under its guide, one launch, masked in its epilogue
+                        lg = self.guided[id(s)]["lg"]
+                        self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + lg.g.shape[0] * c * c * 4, lambda: hip.gram_guided_bwd_masked(
+                            self.dmat[id(s)], f, lg.g, lg.scale, self.mean[id(s)], g[s.src], acc, relu_mask=rm))
+                    else:
+                        self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + c * c * 4, lambda: hip.gram_bwd(
+                            self.dmat[id(s)], f, self.mean[id(s)], g[s.src], acc, workspace=self.ws, relu_mask=rm))
                     cur = s.src
             elif s.kind == "content":
                 if self._active(s, a[s.src].shape):
@@ -909,6 +997,10 @@ class StyleEngine:
                 key.append((s.kind, id(m), getattr(m, "mode", None), float(m.strength), bool(getattr(m, "normalize", False)),
                             sig(getattr(m, "target", None)), sig(getattr(m, "video_target", None)), sig(getattr(m, "weights", None)),
                             float(getattr(m, "video_style_factor", 0.0)), bool(getattr(m, "use_covariance", False))))
+                gd = getattr(self, "guided", {}).get(id(s))
+                if gd is not None:  # a guided step: its guides, layer guides, targets (addresses) and coefficient arrays (values)
+                    lg = gd["lg"]
+                    key.append(("guided", sig(getattr(m, "guide", None)), sig(lg.g), sig(lg.scale), sig(lg.mass), sig(gd["target"]), gd["coef"]))
             elif s.kind == "conv":
                 key.append((id(m), m.weight.data_ptr(), m.weight._version))
         key.append(("hint", self.batch_hint, self.independent))

@@ -75,6 +75,9 @@ SIGNATURES = {
     "maua_gram_guided_mass": (c_i, [c_p, c_p, c_i, c_i64, c_p]),
     "maua_gram_guided_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_sz, c_p]),
     "maua_gram_guided_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
+    "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
+    "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
     "maua_tv_fwd_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "maua_fill": (c_i, [c_p, c_i64, c_f, c_p]),
     "maua_depth_to_space": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -904,6 +907,45 @@ def gram_guided_bwd(d_sym, f, guides, coef, mean, gf, accumulate):
         raise HipError("gram_guided_bwd: shapes of d_sym, guides, coef, mean and gf do not agree")
     _check(lib().maua_gram_guided_bwd(_ptr(_f32(d_sym, "d")), _ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(coef, "coef")),
                                       _ptr(_f32(mean, "mean")), _ptr(_f32(gf, "gf")), r, c, hw, int(accumulate), _stream()), "maua_gram_guided_bwd")
+    return gf
+
+
+def gram_guided_mse_ledger_supported(regions, c):
+    """Do the partial sums of gram_guided_fwd_mse_ledger's finishing launch fit one ledger record?  (maua_hip.h states the bound.)"""
+    return bool(lib().maua_guided_gram_mse_ledger_supported(int(regions), int(c)))
+
+
+def gram_guided_fwd_mse_ledger(f, guides, scale, center, mass, out, mean_out, target, dmat, loss_scale, grad_scale, ledger, slot, workspace=None):
+    """gram_guided_fwd into `out` (R,C,C) / `mean_out` (R,C) - the same bits - plus dmat[r] = grad_scale[r] (G_r - target[r]) (symmetric; zeros
+    for a region with scale or grad_scale 0) and the layer's loss sum_r loss_scale[r] sum (G_r - target[r])^2 as record `slot` of `ledger`
+    (one frame's records).  loss_scale, grad_scale: (R,) float32 device tensors."""
+    c = f.shape[1] if f.dim() == 4 else f.shape[0]
+    hw = f.numel() // c
+    r = _guides_2d(guides, hw)
+    if scale.numel() != r or loss_scale.numel() != r or grad_scale.numel() != r or \
+            (center and (mass is None or mass.numel() != r or mass.dtype != torch.float64 or mean_out is None or mean_out.numel() != r * c)):
+        raise HipError("gram_guided_fwd_mse_ledger: one scale, loss_scale, grad_scale (float32) and, to centre, one mass (float64) and C means per region")
+    if out.numel() != r * c * c or target.numel() != r * c * c or dmat.numel() != r * c * c:
+        raise HipError("gram_guided_fwd_mse_ledger: gram, target and dmat are (R, C, C)")
+    workspace = _ws(workspace, gram_guided_workspace_bytes(r, c, hw), f.device)
+    _check(lib().maua_guided_gram_fwd_mse_ledger(
+        _ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(scale, "scale")), _ptr(mass) if center else None, _ptr(_f32(out, "gram")),
+        _ptr(_f32(mean_out, "mean")) if center else None, r, c, hw, int(center), _ptr(_f32(target, "target")), _ptr(_f32(loss_scale, "loss_scale")),
+        _ptr(_f32(grad_scale, "grad_scale")), _ptr(_f32(dmat, "dmat")), ledger.data_ptr(), int(slot), workspace.data_ptr(),
+        workspace.numel() * workspace.element_size(), _stream()), "maua_guided_gram_fwd_mse_ledger")
+    return out, (mean_out if center else None)
+
+
+def gram_guided_bwd_masked(d_sym, f, guides, coef, mean, gf, accumulate, relu_mask=None):
+    """gram_guided_bwd whose result is written as 0 where relu_mask (shaped like gf) is <= 0; None: gram_guided_bwd's bits."""
+    r, c = d_sym.shape[0], d_sym.shape[1]
+    hw = f.numel() // c
+    if _guides_2d(guides, hw) != r or coef.numel() != r or gf.numel() != f.numel() or (mean is not None and mean.numel() != r * c) or \
+            (relu_mask is not None and relu_mask.numel() != gf.numel()):
+        raise HipError("gram_guided_bwd_masked: shapes of d_sym, guides, coef, mean, relu_mask and gf do not agree")
+    _check(lib().maua_guided_gram_bwd_masked(_ptr(_f32(d_sym, "d")), _ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(coef, "coef")),
+                                             _ptr(_f32(mean, "mean")), _ptr(_f32(relu_mask, "relu_mask")), _ptr(_f32(gf, "gf")), r, c, hw,
+                                             int(accumulate), _stream()), "maua_guided_gram_bwd_masked")
     return gf
 
 

@@ -11,7 +11,8 @@ network to engine.StyleEngine, which reads `.target`, `.strength`, `.normalize` 
 chains the kernels without autograd.  Both paths produce the same numbers (tests/test_engine_gpu.py).
 
 Spatial control (not in the reference): a StyleLoss with `guide` set matches one Gram matrix per region of the guides
-(Gatys et al. 2017; csrc/gram_guided.hip).  Such a network runs through these modules only.
+(Gatys et al. 2017; csrc/gram_guided.hip).  Such a network runs through these modules only, unless the planner
+field guided_engine is on (then engine.StyleEngine evaluates it; targets are still captured here).
 """
 import sys
 

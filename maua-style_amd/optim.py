@@ -46,14 +46,15 @@ def _device_guide(guide, image):
 
 
 def _guided(net_or_losses):
-    """Does a style module of the network (or of a list of loss modules) carry guides?  Such a network runs on the module path."""
+    """Does a style module of the network (or of a list of loss modules) carry guides?  Such a network runs on the module path unless the
+    planner field guided_engine is on."""
     mods = getattr(net_or_losses, "style_losses", net_or_losses)
     return any(getattr(m, "guide", None) is not None for m in mods)
 
 
 def _engine_of(net):
     """The fused engine of a loss network (built once per network; None when its module layout is not covered)."""
-    if _guided(net):
+    if _guided(net) and not plan.on("guided_engine"):
         return None  # (not remembered: the same network without guides takes the engine again)
     eng = getattr(net, "_maua_engine", None)
     if eng is None and not getattr(net, "_maua_engine_refused", False):
@@ -190,7 +191,8 @@ class PixelOptimizer:
         self.independent = bool(independent) and init.shape[0] > 1
         self.grad_hook = grad_hook  # in-place edit of the gradient before the optimiser sees it (img_vid's overlap masking)
         try:
-            if _guided(losses):  # (also on the L-BFGS bundle path below: no engine, no bundle, no captured graph)
+            # (also on the L-BFGS bundle path below: no engine, no bundle, no captured graph - unless the planner field guided_engine is on)
+            if _guided(losses) and not plan.on("guided_engine"):
                 raise engine_mod.UnsupportedNet("guided StyleLoss runs on the module path")
             self.engine = getattr(net, "_maua_engine", None) or engine_mod.StyleEngine(net, losses)
             net._maua_engine = self.engine
@@ -211,7 +213,11 @@ class PixelOptimizer:
         if self.engine is not None and self.kind == "lbfgs" and grad_hook is None and plan.on("graph_bundles"):
             self._bundle_key = ("lbfgs", tuple(self.x.shape), str(self.x.device), str(self.x.dtype), self.independent, self.batch_hint,
                                 int(args.lbfgs_num_correction), float(args.lbfgs_tolerance_change), float(args.lbfgs_tolerance_grad))
-            self.engine._prepare(self.x)  # (allocates for this shape if the engine last served another one: a new epoch)
+            try:
+                self.engine._prepare(self.x)  # (allocates for this shape if the engine last served another one: a new epoch)
+            except engine_mod.UnsupportedNet:  # (a guided layer the engine does not take, planner field guided_engine: module path)
+                self.engine, self._bundle_key = None, None
+        if self._bundle_key is not None:
             bundle = self.engine.iter_graphs.get(self._bundle_key)
             if bundle is not None and (bundle["epoch"] != self.engine.alloc_epoch or bundle["graph_key"] != self.engine._graph_key()):
                 bundle = None
@@ -487,7 +493,8 @@ def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep
     the device tensor instead, so that colour matching, rescaling and the next scale run without a host round trip.
     `guides` = (content guides (R,H,W), [style guides (R,H_i,W_i) per style image]), values in [0, 1] at each image's resolution, 1 <= R
     <= 8: spatial control - every style layer matches one Gram matrix per region (loss.StyleLoss.guide) instead of one of the whole plane.
-    One frame only, and the evaluation runs module by module (autograd over the HIP kernels), not through the fused engine."""
+    One frame only; the evaluation runs module by module (autograd over the HIP kernels) unless the planner field guided_engine is on:
+    then the guided layers run inside the fused engine and its captured graph."""
     if guides is not None and ("_vid" in args.transfer_type or init.shape[0] != 1):
         raise NotImplementedError("guides (spatial control of the style loss) are implemented for one image per call (img_img), "
                                   "not for clips or frame batches")

@@ -55,6 +55,7 @@ FIELDS = {
     "frame_cache_mb": ("4096", "host", "vid_img: host cache for decoded frames"),
     "temporal_device": ("0", "host", "vid_img over a flow cache: 1 keeps frames, warp grid, reliability mask and blend on the device (csrc/warp.hip; frames chain through the 8-bit image the PNG holds), 0 the reference's host loop"),
     "clip_device": ("0", "host", "img_vid: 1 keeps the clip on the device between and inside scales (initial filter and temporal blend in csrc/gauss_wrap.hip, windows gathered on the device, frames leave as 8-bit images), 0 the reference's host loop"),
+    "guided_engine": ("0", "host", "img_img with guides (spatial control): 1 runs the guided style layers inside the fused engine and its captured graph (per-region Gram, loss and D matrices in one finishing launch, csrc/gram_guided.hip; B = 1, needs loss_ledger), 0 the module path"),
     "debug_poison": ("0", "host", "tests: every engine buffer starts as NaN"),
     # ---- libmaua_hip (csrc/: maua::tuning)
     "conv_few_out": ("1", "lib", "3x3 passes that produce <= 4 channels run conv3x3_few_out (0: the general MFMA kernel)"),

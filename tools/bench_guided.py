@@ -11,8 +11,12 @@ The variants run interleaved, `--rounds` rounds of `--reps` back-to-back calls b
 gives the median and the minimum over the rounds.  Feature maps are relu(randn): the same data for every variant of a shape.
 
 Job: VGG-19 (seeded synthetic weights), 1024 x 1024, default layers, L-BFGS: iterations per second of `--steps` steps after `--warmup`
-(host clock around a device synchronise) for the guided job (R = 4 hard quadrants), the unguided job on the module path (autograd over the
-HIP kernels - what the guided job is measured against) and the unguided job on the fused engine (the project's normal route).
+(host clock around a device synchronise) for the guided job (R = 4 hard quadrants) on the module path (the default), the same job with the
+planner field guided_engine = 1 (the fused engine; launched eagerly like the other rows, and once more replaying its captured graph), the
+unguided job on the module path (autograd over the HIP kernels) and the unguided job on the fused engine (the project's normal route).
+The kernel table's row "R4 hard, fused finish + masked bwd" is the engine's form of the layer: the forward call whose finishing launch also
+forms the MSE, the D matrices and the ledger record (its distance to "R4 hard" is what the fused finish costs over the plain one), and the
+backward call with the ReLU mask in its epilogue.
 
     python tools/bench_guided.py [--rounds 7] [--reps 10] [--steps 20] [--warmup 3] [--size 1024] > profiles/bench_guided.md
 """
@@ -73,6 +77,15 @@ def kernel_table(a, out):
             keep.append((g, mass, scale, ws, grams, d))
             variants[label] = (lambda g=g, scale=scale, mass=mass, ws=ws, grams=grams: hip.gram_guided_fwd(f, g, scale, False, mass, out=grams, workspace=ws),
                                lambda g=g, scale=scale, d=d: hip.gram_guided_bwd(d, f, g, scale, None, gf, False))
+            if label == "R4 hard":  # the engine's form of the layer: finishing launch with the MSE, D and the ledger record; masked backward
+                target, dmat = torch.zeros(R, C, C, device="cuda"), torch.empty(R, C, C, device="cuda")
+                ls, gs = torch.full((R,), 1.0 / (C * C), device="cuda"), torch.full((R,), 4.0 / (C * C), device="cuda")
+                led = hip.loss_ledger(1, 1, f.device)
+                keep.append((target, dmat, ls, gs, led))
+                variants["R4 hard, fused finish + masked bwd"] = (
+                    lambda g=g, scale=scale, mass=mass, ws=ws, grams=grams, target=target, dmat=dmat, ls=ls, gs=gs, led=led:
+                    hip.gram_guided_fwd_mse_ledger(f, g, scale, False, mass, grams, None, target, dmat, ls, gs, led[0], 0, workspace=ws),
+                    lambda g=g, scale=scale, d=d: hip.gram_guided_bwd_masked(d, f, g, scale, None, gf, False, relu_mask=f))
         times = {k: ([], []) for k in variants}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         for rnd in range(a.rounds + 1):  # round 0 warms up
@@ -112,9 +125,16 @@ def job_rates(a, out):
     content, style, init = synth.images(S)
     guides = (hard_guides(4, S, S), [hard_guides(4, S, S)])
     rates = {}
-    for label in ("guided, R = 4 hard quadrants (module path)", "unguided, module path", "unguided, fused engine"):
+    import plan
+    for label in ("guided, R = 4 hard quadrants (module path)", "guided, R = 4 hard quadrants, guided_engine=1 (fused engine)",
+                  "guided, R = 4 hard quadrants, guided_engine=1 (fused engine, captured graph)", "unguided, module path", "unguided, fused engine"):
+        plan.OVERRIDES.pop("guided_engine", None)
+        if "guided_engine=1" in label:  # (what MAUA_PLAN="guided_engine=1" sets)
+            plan.OVERRIDES["guided_engine"] = "1"
         args = config.get_args(["--content", "c.png", "--style", "s.png", "--model_file", wfile, "--disable_check", "--scaling_args", scaling,
                                 "--image_sizes", str(S), "--num_iters", str(a.steps), "--seed", "0", "--no_hist_match"])
+        if "captured graph" in label:
+            args.hip_graph = 1  # (a job of 128 iterations or more takes the graph by itself; the other rows launch eagerly)
         optim.set_model_args(args, S)
         net, losses = models.load_model(args)
         optim.set_content_targets(net, content, args)
@@ -127,7 +147,7 @@ def job_rates(a, out):
         opt = optim.PixelOptimizer(net, losses, init, args, planned_iters=a.steps + a.warmup)
         if "module path" in label:
             opt.engine = None
-        assert (opt.engine is not None) == ("fused" in label)
+        assert (opt.engine is not None) == ("fused" in label), label
         for _ in range(a.warmup):
             opt.step()
         torch.cuda.synchronize()
@@ -139,6 +159,7 @@ def job_rates(a, out):
         print(json.dumps(dict(job=label, size=S, steps=a.steps, iterations_per_s=rates[label])), file=sys.stderr, flush=True)
         del opt, net, losses
         torch.cuda.empty_cache()
+    plan.OVERRIDES.pop("guided_engine", None)
     out.append("| job | iterations/s |")
     out.append("|---|---|")
     for k, v in rates.items():

@@ -103,6 +103,12 @@ def main():
                                    ptr, ws_bytes, None),
             L.maua_gram_guided_bwd(ptr, ptr, ptr, ptr, rng.choice([None, ptr]), ptr, rng.choice([1, 3, 8, 0, 9, -1]), cin,
                                    h * w if abs(h * w) < 1 << 40 else 1, case % 2, None),
+            # (region counts, slots and nullable pointers of these three follow the case number: the random stream of the calls around stays as it was)
+            L.maua_guided_gram_mse_ledger_supported((1, 8, 0, 9, -1)[case % 5], cin),
+            L.maua_guided_gram_fwd_mse_ledger(ptr, ptr, ptr, ptr, ptr, ptr, (1, 3, 8, 0, 9, -1)[case % 6], cin, h * w if abs(h * w) < 1 << 40 else 1,
+                                              case % 2, ptr, ptr, ptr, ptr, ptr, (0, 3, -1)[case % 3], ptr, ws_bytes, None),
+            L.maua_guided_gram_bwd_masked(ptr, ptr, ptr, ptr, (None, ptr)[case % 2], (None, ptr)[case // 2 % 2], ptr, (1, 3, 8, 0, 9, -1)[case // 3 % 6], cin,
+                                          h * w if abs(h * w) < 1 << 40 else 1, case % 2, None),
             L.maua_tv_fwd_bwd(ptr, ptr, n, cin, h, w, 1.0, 0, ptr, ptr, ws_bytes, None),
             L.maua_resize_bilinear(ptr, ptr, n, h, w, cout, cin, 0.5, 0.5, None),
             L.maua_channel_stats(ptr, None, 1e-3, n, rng.randint(-1, 3), h, w, ptr, ptr, ws_bytes, None),
