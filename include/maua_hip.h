@@ -374,6 +374,27 @@ int maua_guided_gram_fwd_mse_ledger(const float* f, const float* guides, const f
 int maua_guided_gram_bwd_masked(const float* d_sym, const float* f, const float* guides, const float* coef, const float* mean,
                                 const float* relu_mask, float* gf, int regions, int c, int64_t hw, int accumulate, maua_stream_t stream);
 
+/* ---- shifted Gram matrices: products of a feature map with a translated copy of itself (gram_shift.hip) ------- */
+/* Long-range consistency of the style loss (Berger & Memisevic 2016): `shifts` (1 .. 16) translations of one style layer f[C][h][w], each
+ * (axes[s], deltas[s]) with axes[s] 0 = x, 1 = y and 1 <= deltas[s] < the axis extent.  With X = f - mean (mean[C] nullable: no centring),
+ * pixel index p = y w + x, off_s = deltas[s] (x) or deltas[s] * w (y), and p valid for s where x < w - deltas[s] (x) or y < h - deltas[s] (y):
+ *     gram[s][c][k] = scales[s] * sum_{p valid for s} X[c][p + off_s] * X[k][p]                       (NOT symmetric)
+ * maua_gram_shift_fwd: split-K over the plane with a fixed-order fp64 reduction (same inputs, same bits; a shift has the same bits
+ *   alone or among others); fp32-MFMA arithmetic.  workspace: maua_gram_shift_workspace_bytes(shifts, C, h, w) bytes (0 for a refused shape).
+ * maua_gram_shift_bwd: gx[C][h w] (+)= sum_s coefs[s] * ( [q - off_s valid] sum_k d[s][c][k] X[k][q - off_s]
+ *                                                       + [q valid] sum_k d[s][k][c] X[k][q + off_s] ),
+ *   d[shifts][C][C] as given (not symmetrised).  With accumulate == 0 every element of gx is written.  One launch, no workspace.  gx is the
+ *   gradient with respect to X; the term through `mean` (minus the row means of gx) is the caller's.
+ * axes, deltas, scales and coefs are HOST arrays of `shifts` entries (copied into the launch arguments).  No element outside f is read.
+ * Any C >= 1 (up to 65536), h, w >= 1 with h w < 2^30; other shapes, shift counts, axes and deltas return MAUA_E_UNSUPPORTED, null pointers
+ * MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before any launch. */
+int maua_gram_shift_supported(int shifts, int c, int h, int w);
+size_t maua_gram_shift_workspace_bytes(int shifts, int c, int h, int w);
+int maua_gram_shift_fwd(const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram, int shifts,
+                        int c, int h, int w, void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_gram_shift_bwd(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs, float* gx,
+                        int shifts, int c, int h, int w, int accumulate, maua_stream_t stream);
+
 /* ---- total variation: loss.TVLoss.forward, loss.py:224-233, and its autograd ---------------------- */
 /* loss_out[0] = strength * (sum|dy| + sum|dx|); grad (+)= strength * d/dx.  workspace as for the MSE. */
 int maua_tv_fwd_bwd(const float* x, float* grad, int n, int c, int h, int w, float strength, int accumulate,

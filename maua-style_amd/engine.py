@@ -102,6 +102,8 @@ class StyleEngine:
             elif isinstance(m, loss_mod.StyleLoss):
                 if getattr(m, "guide", None) is not None and not plan.on("guided_engine"):
                     raise UnsupportedNet("guided StyleLoss runs on the module path")
+                if m.shift_factor > 0:
+                    raise UnsupportedNet("shifted StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -468,6 +470,8 @@ class StyleEngine:
                     raise RuntimeError(f"{getattr(m, 'name', 'StyleLoss')}: guided style target not captured")
                 raise ValueError("guided StyleLoss: content and style guides must name the same regions")
             return True
+        if m.shift_factor > 0:  # (set after the plan was made: no engine evaluation without the shift terms)
+            raise UnsupportedNet("shifted StyleLoss runs on the module path")
         if m.target.nelement() == 0:
             raise RuntimeError(f"{m.name}: style target not captured")
         if shapes_src[0] == 1 and m.video_style_factor > 0 and m.video_target.nelement() != 0 \

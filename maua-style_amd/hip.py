@@ -75,6 +75,10 @@ SIGNATURES = {
     "maua_gram_guided_mass": (c_i, [c_p, c_p, c_i, c_i64, c_p]),
     "maua_gram_guided_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_sz, c_p]),
     "maua_gram_guided_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
+    "maua_gram_shift_supported": (c_i, [c_i, c_i, c_i, c_i]),
+    "maua_gram_shift_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "maua_gram_shift_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_gram_shift_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
@@ -908,6 +912,54 @@ def gram_guided_bwd(d_sym, f, guides, coef, mean, gf, accumulate):
     _check(lib().maua_gram_guided_bwd(_ptr(_f32(d_sym, "d")), _ptr(_f32(f, "f")), _ptr(_f32(guides, "guides")), _ptr(_f32(coef, "coef")),
                                       _ptr(_f32(mean, "mean")), _ptr(_f32(gf, "gf")), r, c, hw, int(accumulate), _stream()), "maua_gram_guided_bwd")
     return gf
+
+
+def gram_shift_supported(shifts, c, h, w):
+    return bool(lib().maua_gram_shift_supported(int(shifts), int(c), int(h), int(w)))
+
+
+def gram_shift_workspace_bytes(shifts, c, h, w):
+    return lib().maua_gram_shift_workspace_bytes(int(shifts), int(c), int(h), int(w))
+
+
+def _shift_args(shifts, factors):
+    """shifts: [(axis, delta), ...] with axis 0 = x, 1 = y -> the three host arrays of the gram_shift entry points."""
+    n = len(shifts)
+    if n != len(factors):
+        raise HipError(f"{n} shifts and {len(factors)} factors")
+    return ((ctypes.c_int * n)(*[int(a) for a, _ in shifts]), (ctypes.c_int * n)(*[int(d) for _, d in shifts]),
+            (ctypes.c_double * n)(*[float(v) for v in factors]))
+
+
+def gram_shift_fwd(f, shifts, scales, mean=None, out=None, workspace=None):
+    """f: (1,C,H,W) or (C,H,W); shifts: [(axis, delta), ...]; scales: one float per shift; mean: (C,) row means to subtract or None.
+    Returns grams (S,C,C), gram[s][c][k] = scales[s] sum_p X[c][p + off_s] X[k][p] over the pairs inside the map."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    if f.numel() != c * h * w or (mean is not None and mean.numel() != c):
+        raise HipError("gram_shift_fwd: f is one (C, H, W) map and mean holds C values")
+    n = len(shifts)
+    axes, deltas, fac = _shift_args(shifts, scales)
+    if out is None:
+        out = torch.empty(n, c, c, device=f.device, dtype=torch.float32)
+    elif out.numel() != n * c * c:
+        raise HipError("gram_shift_fwd: out is (S, C, C)")
+    workspace = _ws(workspace, gram_shift_workspace_bytes(n, c, h, w), f.device)
+    _check(lib().maua_gram_shift_fwd(_ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), axes, deltas, fac, _ptr(_f32(out, "out")), n, c, h, w,
+                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()), "maua_gram_shift_fwd")
+    return out
+
+
+def gram_shift_bwd(d, f, shifts, coefs, mean, gx, accumulate):
+    """gx (+)= sum_s coefs[s] (d[s] X shifted back by off_s + d[s]^T X shifted on by off_s), X = f - mean; d: (S,C,C) as given (not
+    symmetrised).  The gradient with respect to X: the caller subtracts the row means of gx in the covariance form."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(shifts)
+    if f.numel() != c * h * w or d.numel() != n * c * c or gx.numel() != f.numel() or (mean is not None and mean.numel() != c):
+        raise HipError("gram_shift_bwd: shapes of d, f, mean and gx do not agree")
+    axes, deltas, fac = _shift_args(shifts, coefs)
+    _check(lib().maua_gram_shift_bwd(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), axes, deltas, fac, _ptr(_f32(gx, "gx")),
+                                     n, c, h, w, int(accumulate), _stream()), "maua_gram_shift_bwd")
+    return gx
 
 
 def gram_guided_mse_ledger_supported(regions, c):

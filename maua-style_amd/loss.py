@@ -13,6 +13,9 @@ chains the kernels without autograd.  Both paths produce the same numbers (tests
 Spatial control (not in the reference): a StyleLoss with `guide` set matches one Gram matrix per region of the guides
 (Gatys et al. 2017; csrc/gram_guided.hip).  Such a network runs through these modules only, unless the planner
 field guided_engine is on (then engine.StyleEngine evaluates it; targets are still captured here).
+
+Long-range consistency (--shift_factor; Berger & Memisevic 2016): with `shift_factor > 0` a StyleLoss also matches the products of the
+activation with translated copies of itself (csrc/gram_shift.hip).  Such a network runs through these modules only.
 """
 import sys
 
@@ -117,6 +120,56 @@ class _GuidedGramFn(torch.autograd.Function):
         return gf, None, None, None, None
 
 
+def shift_deltas(h, w):
+    """The translations of a style layer of h x w pixels: the reference's list 4 ** range(1, int(log2(n) / 2 - 0.5)) on the shorter side n
+    ([] below 32, [4] up to 127, [4, 16] up to 511, ...; every delta <= n / 8)."""
+    n = min(int(h), int(w))
+    if n < 1:
+        return []
+    return [int(d) for d in 4 ** np.array(range(1, int(np.log2(n) / 2 - 0.5)))]
+
+
+def shift_pairs(axis, delta, h, w):
+    """Number of pixel pairs (p, p + offset) of the shift inside an h x w map."""
+    return h * (w - delta) if axis == 0 else (h - delta) * w
+
+
+class _ShiftGramFn(torch.autograd.Function):
+    """G_s[c][k] = scale_s sum_p X[c][p + off_s] X[k][p] for the shifts [(axis, delta), ...] of one frame x (1, C, H, W), X = x - mu (mu: the
+    map's row means in the covariance form, else 0), over the pairs inside the map; scale_s = 1 / (C n_s) where `scales` is None (apply takes all four arguments).
+    Backward: hip.gram_shift_bwd (dL/dX) and, in the covariance form, minus its row means - the crops do not sum to zero."""
+
+    @staticmethod
+    def forward(ctx, x, shifts, use_covariance, scales):
+        B, C, H, W = x.shape
+        if B != 1:
+            raise ValueError("shifted Gram matrices: one frame per call (B = 1)")
+        shifts = [(int(a), int(d)) for a, d in shifts]
+        if scales is None:
+            scales = [1.0 / (C * shift_pairs(a, d, H, W)) for a, d in shifts]
+        xc = x.contiguous()
+        mean = None
+        if use_covariance:
+            mean = torch.empty(C, device=x.device, dtype=torch.float32)
+            hip.gram_row_means(xc, mean, hip._ws(None, hip.gram_workspace_bytes(C, H * W), x.device))
+        grams = hip.gram_shift_fwd(xc, shifts, scales, mean)
+        ctx.save_for_backward(xc)
+        ctx.mean, ctx.shifts, ctx.scales = mean, shifts, list(scales)
+        return grams
+
+    @staticmethod
+    def backward(ctx, g):
+        (xc,) = ctx.saved_tensors
+        gx = torch.empty_like(xc)
+        hip.gram_shift_bwd(g.contiguous(), xc, ctx.shifts, ctx.scales, ctx.mean, gx, False)
+        if ctx.mean is not None:
+            C, hw = xc.shape[1], xc.shape[2] * xc.shape[3]
+            rm = torch.empty(C, device=xc.device, dtype=torch.float32)
+            hip.gram_row_means(gx, rm, hip._ws(None, hip.gram_workspace_bytes(C, hw), xc.device))
+            gx = gx - rm.reshape(1, C, 1, 1)
+        return gx, None, None, None
+
+
 class LayerGuides:
     """The guides of one style layer: `g` (R, H_l W_l) = the image-resolution guides resized to the activation with the project's bilinear
     kernel, `mass` N_r = sum g_r^2 (device, fp64; `mass_host` its one read-back), `active` = [N_r >= 1] and `scale` = 1 / (C N_r) on the
@@ -186,11 +239,20 @@ class ContentLoss(nn.Module):
 
 
 class GramMatrix(nn.Module):
-    """(B*C) x (B*C) Gram matrix of a feature batch, or its covariance form (reference loss.py:67-91).  The
-    shift/flip arguments exist in the reference's signature but its code always ends with y = x (and its
-    `::-1` slices are illegal in torch), so they are accepted and have no effect here either."""
+    """(B*C) x (B*C) Gram matrix of a feature batch, or its covariance form (reference loss.py:67-91).  With exactly one of
+    `shift_x` / `shift_y` nonzero (one frame, B = 1): the raw shifted product X_A X_B^T of the map with itself translated by that many
+    pixels along the axis, X_A[c] = X[c] at p + offset, X_B[k] = X[k] at p, over the pairs inside the map (not symmetric; X is centred on
+    the whole map's row means in the covariance form).  The reference's own code for these arguments always ends with y = x (and its
+    `::-1` slices are illegal in torch); `shift_t` and the flip arguments are accepted and have no effect."""
 
     def forward(self, x, shift_x=0, shift_y=0, shift_t=0, flip_h=False, flip_v=False, use_covariance=False):
+        if shift_x or shift_y:
+            if shift_x and shift_y:
+                raise ValueError("GramMatrix: one of shift_x / shift_y at a time")
+            if x.shape[0] != 1:
+                raise ValueError("GramMatrix: a shifted product needs one frame (B = 1)")
+            shift = (0, int(shift_x)) if shift_x else (1, int(shift_y))
+            return _ShiftGramFn.apply(x, [shift], use_covariance, [1.0])[0]
         return _GramFn.apply(x, use_covariance)
 
 
@@ -220,8 +282,11 @@ class StyleLoss(nn.Module):
     def reset_targets(self):
         self.target = torch.Tensor()
         self.video_target = torch.Tensor()
-        self.shift_targets_x = []
-        self.shift_targets_y = []
+        self.shift_targets_x = []  # one (C, C) target per entry of shift_target_deltas: sum of blend weight x shifted Gram along x
+        self.shift_targets_y = []  # ... along y
+        self.shift_target_deltas = None  # the deltas every capture pass so far produced (None: nothing captured)
+        self._shift_dropped = set()  # deltas some capture pass produced and another did not
+        self._shift_named = set()
         self.guided_target = None  # (R, C, C): sum over the style images of blend weight x guided Gram, per region
         self.guided_weight = None  # R blend-weight sums over the style images in which the region is active
         self._guided_ready = None
@@ -299,6 +364,8 @@ class StyleLoss(nn.Module):
         if self.mode == "none":
             return input
         if self._guide is not None:
+            if self.shift_factor > 0:
+                raise NotImplementedError("StyleLoss: guides and shift_factor > 0 together are not implemented")
             self.guided_loss(input)
             return input
         self.static_loss(input)
@@ -321,7 +388,59 @@ class StyleLoss(nn.Module):
                 contrib = self.blend_weight * gram.detach() / frames
                 self.target = contrib if self.target.nelement() == 0 else self.target + contrib
             if self.mode == "loss":
-                self.loss += self._accumulate(self.crit(gram, self.target)) * self.strength / frames
+                t = self.crit(gram, self.target)
+                if self.shift_factor > 0:
+                    t = self._shift_terms(frame, t)
+                self.loss += self._accumulate(t) * self.strength / frames
+            if self.mode == "capture" and self.shift_factor > 0:
+                self._shift_capture(frame, frames)
+
+    # -- long-range consistency (shift_factor > 0): G_s of loss.shift_deltas(H, W) along x and y, matched like the static Gram matrix
+    def _shift_grams(self, frame, deltas):
+        shifts = [(axis, d) for d in deltas for axis in (0, 1)]
+        return _ShiftGramFn.apply(frame, shifts, bool(self.use_covariance), None)  # rows 2 i, 2 i + 1: deltas[i] along x, y
+
+    def _shift_capture(self, frame, frames):
+        deltas = shift_deltas(frame.shape[2], frame.shape[3])
+        if self.shift_target_deltas is None:
+            C = frame.shape[1]
+            self.shift_target_deltas = list(deltas)
+            self.shift_targets_x = [torch.zeros(C, C, device=frame.device) for _ in deltas]
+            self.shift_targets_y = [torch.zeros(C, C, device=frame.device) for _ in deltas]
+        keep = [d for d in self.shift_target_deltas if d in deltas]
+        self._shift_dropped |= (set(deltas) | set(self.shift_target_deltas)) - set(keep)
+        at = [self.shift_target_deltas.index(d) for d in keep]
+        self.shift_targets_x = [self.shift_targets_x[i] for i in at]
+        self.shift_targets_y = [self.shift_targets_y[i] for i in at]
+        self.shift_target_deltas = keep
+        if keep:
+            grams = self._shift_grams(frame, keep).detach()
+            for i in range(len(keep)):
+                self.shift_targets_x[i] = self.shift_targets_x[i] + self.blend_weight * grams[2 * i] / frames
+                self.shift_targets_y[i] = self.shift_targets_y[i] + self.blend_weight * grams[2 * i + 1] / frames
+
+    def shift_deltas_used(self, h, w):
+        """The deltas of the shift terms for a working layer of h x w: those every capture pass produced and this layer has.  Any other
+        delta of either side is dropped and named once on stderr."""
+        if self.shift_target_deltas is None:
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: shift targets not captured")
+        here = shift_deltas(h, w)
+        use = [d for d in self.shift_target_deltas if d in here]
+        for d in sorted((set(here) | set(self.shift_target_deltas) | self._shift_dropped) - set(use) - self._shift_named):
+            self._shift_named.add(d)
+            print(f"{getattr(self, 'name', 'StyleLoss')}: shift {d} is not produced by every style image and the working image here: "
+                  "no shift term for it", file=sys.stderr)
+        return use
+
+    def _shift_terms(self, frame, t):
+        use = self.shift_deltas_used(frame.shape[2], frame.shape[3])
+        if not use:
+            return t
+        grams = self._shift_grams(frame, use)
+        for i, d in enumerate(use):
+            at = self.shift_target_deltas.index(d)
+            t = t + self.shift_factor * (self.crit(grams[2 * i], self.shift_targets_x[at]) + self.crit(grams[2 * i + 1], self.shift_targets_y[at]))
+        return t
 
     def dynamic_loss(self, input):
         rows = input.shape[0] * input.shape[1]

@@ -52,10 +52,23 @@ def _guided(net_or_losses):
     return any(getattr(m, "guide", None) is not None for m in mods)
 
 
+def _shifted(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) have shift_factor > 0?  Such a network runs on the module path."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(isinstance(m, loss_mod.StyleLoss) and m.shift_factor > 0 for m in mods)
+
+
+def _style_targets_missing(net):
+    """A style module without its target - or, with shift_factor > 0, without its shift targets (the factor was set after the capture)."""
+    return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None) for m in net.style_losses)
+
+
 def _engine_of(net):
     """The fused engine of a loss network (built once per network; None when its module layout is not covered)."""
     if _guided(net) and not plan.on("guided_engine"):
         return None  # (not remembered: the same network without guides takes the engine again)
+    if _shifted(net):
+        return None  # (not remembered either: the same network with shift_factor 0 takes the engine again)
     eng = getattr(net, "_maua_engine", None)
     if eng is None and not getattr(net, "_maua_engine_refused", False):
         if not all(hasattr(net, a) for a in ("content_losses", "style_losses", "tv_losses", "temporal_losses")):
@@ -194,6 +207,8 @@ class PixelOptimizer:
             # (also on the L-BFGS bundle path below: no engine, no bundle, no captured graph - unless the planner field guided_engine is on)
             if _guided(losses) and not plan.on("guided_engine"):
                 raise engine_mod.UnsupportedNet("guided StyleLoss runs on the module path")
+            if _shifted(losses):
+                raise engine_mod.UnsupportedNet("shifted StyleLoss runs on the module path")
             self.engine = getattr(net, "_maua_engine", None) or engine_mod.StyleEngine(net, losses)
             net._maua_engine = self.engine
         except engine_mod.UnsupportedNet:
@@ -470,7 +485,7 @@ def optimize_frames(contents, styles, inits, num_iters, args, net, losses, plann
         PBAR.refresh()
     set_content_targets(net, contents, args)
     key = (tuple((s.data_ptr(), tuple(s.shape), s._version) for s in styles), tuple(args.style_blend_weights))
-    if getattr(net, "_maua_style_key", None) != key or any(m.target.nelement() == 0 for m in net.style_losses):
+    if getattr(net, "_maua_style_key", None) != key or _style_targets_missing(net):
         set_style_targets(net, styles, args)
         net._maua_style_key = key
         net._maua_style_refs = list(styles)
@@ -536,7 +551,7 @@ def optimize(content, styles, init, num_iters, args, net=None, losses=None, keep
             for mod in net.style_losses:
                 mod.guide = None
             net._maua_style_key = None
-        if getattr(net, "_maua_style_key", None) != key or any(m.target.nelement() == 0 for m in net.style_losses):
+        if getattr(net, "_maua_style_key", None) != key or _style_targets_missing(net):
             set_style_targets(net, styles, args)
             net._maua_style_key = key
             net._maua_style_refs = list(styles)  # keep the tensors alive so that data_ptr stays unique
