@@ -937,6 +937,9 @@ static int x3p_choose_split(const ConvArgs& a) {
     const int forced = (int)tuning("x3p_ks", 0);
     // (every split gets chunks: ks is brought down to the number of non-empty ranges of ceil(nchunks / ks) chunks)
     auto whole = [&](int ks) { const int cps = (nchunks + ks - 1) / ks; return (nchunks + cps - 1) / cps; };
+    // (fewer than 32 consumed channels - the image layer, whose workspace the engine asks every family for: no chunk to split, and
+    //  `whole` would divide by zero chunks per split under a forced x3p_ks)
+    if (nchunks < 1) return 1;
     if (forced > 0) return whole(forced <= nchunks / 2 ? forced : (nchunks >= 4 ? nchunks / 2 : 1));
     if (items >= 512 || nchunks < 4) return 1;
     const double out_mb = (double)split_batch_hint() * a.Cout * a.OH * a.OW * 4.0 / 1e6;

@@ -410,15 +410,13 @@ class _ByteBudget(dict):
         self.budget, self.held = int(budget), 0
 
     def __setitem__(self, key, t):
-        if key in self:
-            self.held -= super().__getitem__(key).numel() * super().__getitem__(key).element_size()
+        # (a key that is set again becomes the newest entry: left at its old place in dict order it could be the oldest one, and the
+        #  loop below - which never drops the entry just set - would stop there with the budget still exceeded)
+        self.pop(key, None)
         super().__setitem__(key, t)
         self.held += t.numel() * t.element_size()
         while self.held > self.budget and len(self) > 1:
-            oldest = next(iter(self))
-            if oldest == key:
-                break
-            self.pop(oldest)
+            self.pop(next(iter(self)))
 
     def pop(self, key, *default):
         if key in self:

@@ -408,6 +408,128 @@ def test_every_library_tuning_constant_has_a_test_of_its_other_setting():
         assert field in text, where
 
 
+def test_every_host_planner_field_has_a_test_of_its_other_setting():
+    """The twin for the "host" fields of plan.FIELDS (the switches models.py, engine.py and optim.py read): each is either evaluated
+    through the engine at non-default values by tests/test_plan_variants_gpu.py (`HOST_VARIANTS`) or named with the existing test that
+    forces it (`HOST_COVERED_ELSEWHERE`) - in exactly one of the two tables; the named tests exist and their files name the field, and no
+    value listed as a variant is the field's default (compared as strings: conv_x6 and style_stream are not numbers).  A host field
+    added without a test of its other setting fails here."""
+    import re
+    import plan
+    import test_plan_variants_gpu as pv
+    host_fields = {k for k, (_, who, _) in plan.FIELDS.items() if who == "host"}
+    assert not set(pv.HOST_VARIANTS) & set(pv.HOST_COVERED_ELSEWHERE)
+    assert set(pv.HOST_VARIANTS) | set(pv.HOST_COVERED_ELSEWHERE) == host_fields
+    for field, values in pv.HOST_VARIANTS.items():
+        assert len(values) > 0 and all(str(v) != plan.FIELDS[field][0] for v in values), field
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for field, where in pv.HOST_COVERED_ELSEWHERE.items():
+        path, name = where.split("::")
+        text = open(os.path.join(repo, path)).read()
+        assert re.search(rf"^def {re.escape(name)}\(", text, re.M), where
+        assert field in text.lower(), where   # (four fields have an environment variable of their own: MAUA_<FIELD>)
+    # ... and every variant is run by a test of that module: its parametrisations are built from the table
+    assert {f for f, _ in pv.KIND_A_CASES} | {f for f, _ in pv.KIND_B_CASES} == set(pv.HOST_VARIANTS)
+    for field, values in pv.HOST_VARIANTS.items():
+        ran = {str(v) for f, v in pv.KIND_A_CASES + pv.KIND_B_CASES if f == field}
+        assert ran == {str(v) for v in values}, field
+
+
+def test_forced_x3p_split_answers_for_layers_without_a_whole_chunk():
+    """The engine asks every 3x3 family for its workspace, the image layer's geometry (3 consumed channels: no 32-channel chunk)
+    included.  With the tuning constant x3p_ks forced - MAUA_PLAN="x3p_ks=1", what tests/test_plan_variants_gpu.py sets to route
+    conv_x3p on small planes - conv_x3p's split rule divided by its zero chunks per split and the process died of SIGFPE in
+    StyleEngine._prepare.  Host code: no GPU."""
+    import hip
+    import plan
+    lib = hip.lib()
+    try:
+        for forced in (1, 2, 4):
+            plan.OVERRIDES["x3p_ks"] = str(forced)
+            plan.forward_to_library(lib)
+            for cin in (1, 3, 8, 31):
+                assert hip.conv_x3p_split(1, cin, 72, 72, 64, 1) == 1
+                assert hip.conv_x3p_workspace_bytes(1, cin, 72, 72, 64, 1) == 0
+            assert hip.conv_x3p_split(1, 256, 18, 18, 256, 1) == min(forced, 4)
+    finally:
+        plan.OVERRIDES.pop("x3p_ks", None)
+        plan.forward_to_library(lib)
+
+
+class _Bytes:
+    """What style._ByteBudget asks of an entry: numel() and element_size()."""
+
+    def __init__(self, nbytes, size=4):
+        assert nbytes % size == 0
+        self.n, self.size = nbytes // size, size
+
+    def numel(self):
+        return self.n
+
+    def element_size(self):
+        return self.size
+
+
+def _budget_invariants(cache, newest=None):
+    held = sum(t.numel() * t.element_size() for t in cache.values())
+    assert cache.held == held, (cache.held, held)
+    assert len(cache) <= 1 or cache.held <= cache.budget, (list(cache), cache.held, cache.budget)
+    if newest is not None:
+        assert newest in cache and next(reversed(cache)) == newest
+
+
+@pytest.mark.parametrize("entries", [0, 1, 3])
+def test_frame_cache_budget_holds_under_inserts_overwrites_and_pops(entries):
+    """style._ByteBudget (the device caches of vid_img behind the planner field frame_cache_mb: decoded content frames, written 8-bit
+    frames) with a budget of 0, one and three entries of 400 bytes: after every insert, overwrite of an existing key and pop, `held` is
+    the bytes actually held, the entry just set is there (a single entry larger than the budget stays: the caller is about to use it)
+    and `held <= budget` whenever more than one entry remains."""
+    import random
+    import style
+    cache = style._ByteBudget(400 * entries)
+    r = random.Random(entries)
+    for step in range(400):
+        key = r.randrange(6)
+        what = r.random()
+        if what < 0.6:
+            cache[key] = _Bytes(r.choice([4, 200, 400, 404, 800]), r.choice([1, 4]))
+            _budget_invariants(cache, key)
+            assert len(cache) <= max(entries, 1) or cache.held <= cache.budget
+        elif what < 0.9:
+            had = key in cache
+            assert (cache.pop(key, None) is not None) == had
+            _budget_invariants(cache)
+        else:
+            cache.clear()
+            assert cache.held == 0 and len(cache) == 0
+    with pytest.raises(KeyError):
+        cache.pop("absent")
+
+
+def test_frame_cache_overwrite_of_the_oldest_key_still_meets_the_budget():
+    """The overwrite path: a key that is set again used to keep its old place in dict order, the eviction loop stopped when the oldest
+    entry WAS the key just set, and the cache stayed over its budget with several entries.  Now a re-set key is the newest entry."""
+    import style
+    cache = style._ByteBudget(1200)
+    for k in "abc":
+        cache[k] = _Bytes(400)
+    assert list(cache) == ["a", "b", "c"] and cache.held == 1200
+    cache["a"] = _Bytes(800)               # the oldest key grows: 1600 bytes held before eviction
+    _budget_invariants(cache, "a")
+    assert list(cache) == ["c", "a"] and cache.held == 1200
+    cache["c"] = _Bytes(2000)              # larger than the whole budget: everything else goes, the entry itself stays
+    _budget_invariants(cache, "c")
+    assert list(cache) == ["c"] and cache.held == 2000
+    cache["c"] = _Bytes(400)               # overwriting the only entry
+    _budget_invariants(cache, "c")
+    assert cache.held == 400
+    zero = style._ByteBudget(0)
+    zero["x"] = _Bytes(400)
+    zero["y"] = _Bytes(400)
+    _budget_invariants(zero, "y")
+    assert list(zero) == ["y"]
+
+
 def test_bench_line_refuses_a_stopped_optimiser():
     """bench.lbfgs_still_moving: the timed region's rate is only valid if every iteration did its whole work - a raised stop flag makes the
     update kernels return early.  The helper reports {n_iter, stopped, history_len} and raises when a stop rule fired

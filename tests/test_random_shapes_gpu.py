@@ -228,14 +228,13 @@ def _check_random_configuration(weight_files, seed, scale):
     decisions.  Unpinned, a decision within rounding of its boundary can fall on the other side than in fp64 (at
     S = 151 with avg pooling ONE relu2_1 activation of 720 000 is 0 here and 2.7e-5 in fp64 and moves the image gradient by 1.6e-3): the
     unpinned gradient is held to 1e-4 when the engine takes every decision as fp64 does, and the number of decisions it takes otherwise
-    is bounded by the fp32 oracle's on the same inputs."""
+    is bounded by the fp32 oracle's on the same inputs.  The evaluation and the assertions: tests/configuration_check.py (shared with
+    tests/test_plan_variants_gpu.py)."""
     import models
     import optim
     import synth
+    from configuration_check import check_configuration
     from conftest import product_args
-    from engine_decisions import FLIP_FACTOR, FLIP_SLACK, activation_map, count_flips, engine_decisions, oracle_decisions
-    from oracle import OracleNet, build_spec
-    from oracle.style_oracle import loss_order
     S, extra, two_styles, nin = draw_config(seed, scale)
     styles = ("s.png", "t.png") if two_styles else ("s.png",)
     args = product_args(weight_files, extra, model="nin" if nin else "vgg19", S=S, N=3, styles=styles)
@@ -251,56 +250,9 @@ def _check_random_configuration(weight_files, seed, scale):
     for m in losses:
         m.mode = "loss"
     opt = optim.PixelOptimizer(net, losses, init, args)
-    slots, total, grad = opt.feval()
-    torch.cuda.synchronize()
-    slots, grad = slots.clone().cpu(), grad.clone().cpu()
-    assert opt.engine is not None, (seed, S, extra, "evaluated off the fused engine: no decisions to read")
     sd = synth.nin_state_dict() if nin else synth.vgg19_state_dict()
-    threads = torch.get_num_threads()
-    torch.set_num_threads(min(16, os.cpu_count() or 1))   # (fp64 and the decision counts do not depend on it)
-    try:
-        nets = {}
-        for dt in (torch.float64, torch.float32):
-            onet = OracleNet(build_spec(args), sd, dtype=dt)
-            onet.capture_content(content)
-            onet.capture_style(style_images, args.style_blend_weights)
-            if args.normalize_weights:
-                onet.normalize_weights()
-            nets[dt] = onet
-        onet = nets[torch.float64]
-        spec = onet.spec
-        ototal, olosses, ograd = onet.feval(init)
-        acts, aux = onet._forward(init.double())
-        decisions, e_flips = engine_decisions(opt.engine, spec, acts, aux)
-        acts32, aux32 = nets[torch.float32]._forward(init.float())
-        o_flips = count_flips(spec, oracle_decisions(spec, acts32, aux32), acts, aux)
-        del acts32, aux32
-        pacts, _ = onet._forward(init.double(), decisions=decisions)
-        _, _, pgrad = onet.feval(init, decisions=decisions)
-    finally:
-        torch.set_num_threads(threads)
-    order = loss_order(spec)
-    got = slots.tolist()
-    for k, i in enumerate(order):
-        want = float(olosses.get(i, 0.0))
-        assert abs(got[k] - want) <= 1e-4 * max(abs(want), 1e-9), (seed, S, extra, spec[i].name, got[k], want)
-    checked = 0
-    for k, i in activation_map(opt.engine, spec).items():
-        v = opt.engine.act[k]
-        if v.is_meta:
-            continue   # (pooled in the producing launch: only the pooled map exists)
-        err = rel_l2(v.cpu(), pacts[i])
-        assert err <= 2e-6, (seed, S, extra, k, spec[i].kind, err)
-        checked += 1
-    assert checked > 0
-    rel, pinned = rel_l2(grad, ograd), rel_l2(grad, pgrad)
-    e, o = sum(e_flips.values()), sum(o_flips.values())
-    print(f"random configuration {seed} (S = {S}, {'nin' if nin else 'vgg19'}): gradient {rel:.2e} unpinned, {pinned:.2e} pinned; "
-          f"decisions off fp64: engine {e}, fp32 oracle {o}")
-    assert pinned <= 1e-4, (seed, S, extra, pinned, rel, e)
-    assert e <= FLIP_FACTOR * o + FLIP_SLACK, (seed, S, extra, e, o, {spec[i].name or i: n for i, n in e_flips.items() if n})
-    if e == 0:
-        assert rel <= 1e-4, (seed, S, extra, rel)
+    check_configuration(f"random configuration {seed} (S = {S}, {'nin' if nin else 'vgg19'})", (seed, S, extra), args, net, opt, content,
+                        style_images, init, sd)
 
 
 @pytest.mark.parametrize("seed", range(20))
