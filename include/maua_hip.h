@@ -395,6 +395,28 @@ int maua_gram_shift_fwd(const float* f, const float* mean, const int* axes, cons
 int maua_gram_shift_bwd(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs, float* gx,
                         int shifts, int c, int h, int w, int accumulate, maua_stream_t stream);
 
+/* ---- mirrored Gram matrices: products of a feature map with its mirror image (gram_flip.hip) ------------------- */
+/* Symmetry terms of the style loss (Berger & Memisevic 2016): `mirrors` (1 .. 4) mirrors of one style layer f[C][h][w], kinds[m] 0 = LR
+ * (y, w - 1 - x), 1 = UD (h - 1 - y, x), 2 = point mirror / rotation by 180 degrees (h - 1 - y, w - 1 - x); repeats are allowed.  With
+ * X = f - mean (mean[C] nullable: no centring), pixel index p = y w + x and sigma_m the mirror of kinds[m]:
+ *     gram[m][c][k] = scales[m] * sum_p X[c][sigma_m(p)] * X[k][p]           over all h w pixels; symmetric, returned bit-symmetric
+ * maua_gram_flip_fwd: split-K over the plane and the tile pairs on or above the diagonal, with a fixed-order fp64 reduction that writes
+ *   (c, k) and (k, c) from one sum (same inputs, same bits; a mirror has the same bits alone or among others); fp32-MFMA arithmetic.
+ *   workspace: maua_gram_flip_workspace_bytes(mirrors, C, h, w) bytes (0 for a refused shape).
+ * maua_gram_flip_bwd: gx[C][h w] (+)= sum_m coefs[m] * sum_k (d[m][c][k] + d[m][k][c]) X[k][sigma_m(q)],
+ *   d[mirrors][C][C] as given (not symmetrised).  With accumulate == 0 every element of gx is written.  One launch, no workspace.  A mirror
+ *   whose coef is 0 is left out.  gx is the gradient with respect to X and to f alike: the term through `mean` vanishes, since X summed
+ *   over a mirrored plane is X summed over the plane, 0.
+ * kinds, scales and coefs are HOST arrays of `mirrors` entries (copied into the launch arguments).  No element outside f is read.
+ * Any C >= 1 (up to 65536), h, w >= 1 with h w < 2^30; other shapes, mirror counts and kinds return MAUA_E_UNSUPPORTED, null pointers
+ * MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before any launch. */
+int maua_gram_flip_supported(int mirrors, int c, int h, int w);
+size_t maua_gram_flip_workspace_bytes(int mirrors, int c, int h, int w);
+int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c, int h, int w,
+                       void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
+                       int h, int w, int accumulate, maua_stream_t stream);
+
 /* ---- total variation: loss.TVLoss.forward, loss.py:224-233, and its autograd ---------------------- */
 /* loss_out[0] = strength * (sum|dy| + sum|dx|); grad (+)= strength * d/dx.  workspace as for the MSE. */
 int maua_tv_fwd_bwd(const float* x, float* grad, int n, int c, int h, int w, float strength, int accumulate,

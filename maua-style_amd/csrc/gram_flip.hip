@@ -1,0 +1,446 @@
+// Mirrored Gram matrices (Berger & Memisevic 2016, the symmetry terms): for M mirrors of one style layer with activation F[C][H W], X = F - mu
+// (mu: the map's row means in the covariance form, else 0), flat pixel index p = y W + x and the involution sigma_m of the pixel grid
+//     kind 0 (LR): (y, W - 1 - x)      kind 1 (UD): (H - 1 - y, x)      kind 2 (point mirror, 180 degrees): p -> H W - 1 - p
+//     G_m[c][k] = scale_m sum_p X[c][sigma_m(p)] X[k][p]         over ALL pixels; symmetric, and returned bit-symmetric.
+// Backward, D_m = dL/dG_m as given (not symmetrised):
+//     gx[c][q] (+)= sum_m coef_m sum_k (D_m[c][k] + D_m[k][c]) X[k][sigma_m(q)].
+//
+// Forward: gram_shift.hip's fp32-MFMA split-K kernel over the tile pairs ti <= tj only, with the mirror as the third grid dimension.  A stage
+// writes two operands to LDS, X at sigma(p) and X at p, zeros behind the plane's end; the finishing kernel adds the slabs in index order
+// (fp64), applies scale_m and writes (i, j) and (j, i) from the same sum - inside a diagonal tile from the triangle er <= ec only, since the
+// two triangles of an MFMA tile add their products in different orders.  The split of the pixel range depends on (C, H W) only, so a mirror
+// has the same bits alone or among others.
+// Backward: gs_bwd_kernel's layout (64 output channels x 256 pixels per workgroup, 32 input channels per double-buffered LDS stage), one run of
+// stages per mirror: the weight stage holds D_m[k][co] + D_m[co][k], added in registers before the LDS store.
+// The mirrored operand: sigma(p) descends as p ascends (LR, 180), so a pixel quad inside one row is the four consecutive addresses
+// sigma(p) - 3 .. sigma(p), one 16-byte load reversed in registers; UD reads whole rows ascending.  A quad that crosses a row end or the plane's
+// end goes element by element.  sigma(p) lies inside F exactly when p does: the mask of a quad (p < H W) is computed from indices first and
+// decides which addresses are formed at all.
+// hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
+#include <stdlib.h>
+
+#include "fp16x3.hpp"
+
+namespace maua {
+
+constexpr int GF_T = 64;         // tile edge (channels)
+constexpr int GF_K = 64;         // pixels per stage
+constexpr int GF_RS = GF_K + 4;  // LDS row stride (floats), as gram_shift.hip
+constexpr int GF_MMAX = 4;       // most mirrors per call
+constexpr int GF_KMAX = 768;     // most slabs per (mirror, tile pair): a single tile pair (C <= 64) still fills the device
+
+typedef float gf_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+
+struct GfMirrors {  // launch argument: the host arrays of one call
+    int kind[GF_MMAX];
+    double factor[GF_MMAX];  // scale_m (forward) / coef_m (backward)
+};
+
+// bit k: pixel p + k lies below `end`
+__device__ __forceinline__ unsigned gf_mask4(int p, int end) {
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (p + k < end) m |= 1u << k;
+    return m;
+}
+
+// row[p + k] - mu for the elements k of the mask, 0 for the others; only the mask's addresses are formed
+__device__ __forceinline__ f32x4 gf_load4(const float* __restrict__ row, int p, unsigned m, float mu) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (m == 15u) {
+        v = *reinterpret_cast<const gf_f32x4u*>(row + p);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] -= mu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((m >> k) & 1u) v[k] = row[p + k] - mu;
+    }
+    return v;
+}
+
+// row[sigma(p + k)] - mu for the elements k of the mask (all of them below H W), 0 for the others.  (y, x) are the row and column of p.
+__device__ __forceinline__ f32x4 gf_load4_mirror(const float* __restrict__ row, int p, unsigned m, float mu, int kind, int H, int W, int y, int x) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    const int HW = H * W;
+    if (m == 15u && (kind == 2 || x + 3 < W)) {  // the whole quad inside the plane and (LR, UD) inside one row: four consecutive addresses
+        const int a = kind == 2 ? HW - 4 - p : kind == 0 ? y * W + (W - 4 - x) : (H - 1 - y) * W + x;
+        const f32x4 t = *reinterpret_cast<const gf_f32x4u*>(row + a);
+        if (kind == 1) {
+            v = t;
+        } else {
+            v[0] = t[3], v[1] = t[2], v[2] = t[1], v[3] = t[0];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] -= mu;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((m >> k) & 1u) {
+                const int pk = p + k, yy = pk / W, xx = pk - yy * W;
+                const int a = kind == 2 ? HW - 1 - pk : kind == 0 ? yy * W + (W - 1 - xx) : (H - 1 - yy) * W + xx;
+                v[k] = row[a] - mu;
+            }
+    }
+    return v;
+}
+
+// the b-th pair (ti <= tj) of ntile tiles, rows first: (0,0) (0,1) .. (0,n-1) (1,1) ..
+__device__ __forceinline__ void gf_pair(int b, int ntile, int* ti, int* tj) {
+    int i = 0;
+    while (b >= ntile - i) {
+        b -= ntile - i;
+        ++i;
+    }
+    *ti = i;
+    *tj = i + b;
+}
+
+// One workgroup = one mirror x one 64x64 tile pair ti <= tj (ti: rows of G, the operand read at sigma(p); tj: columns, read at p) x one slice
+// of the plane; the four waves own a 32x32 block each.  Slabs: partial[((m npairs + pair) ksplit + ks) 64 64].
+__global__ void __launch_bounds__(256)
+gf_partial_kernel(const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ partial, GfMirrors mr, int C, int H, int W,
+                  int npairs, int ksplit, int chunk) {
+    __shared__ __attribute__((aligned(16))) float At[GF_T * GF_RS];
+    __shared__ __attribute__((aligned(16))) float Bt[GF_T * GF_RS];
+    const int s = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i32 = lane & 31, half = lane >> 5;
+    const int wi = wave >> 1, wj = wave & 1;
+    const int ntile = (C + GF_T - 1) / GF_T;
+    int ti, tj;
+    gf_pair(blockIdx.x, ntile, &ti, &tj);
+    const int ks = blockIdx.y;
+    const int HW = H * W;  // below 2^30
+    const int kind = mr.kind[s];
+    const int p_begin = ks * chunk;  // ks chunk < H W + chunk
+    const int p_end = min(HW, p_begin + chunk);
+
+    constexpr int NL = GF_T * GF_K / 4 / 256;  // 4 quads per tile per thread: rows tid / 16 + 16 q, pixels 4 (tid % 16) .. + 3
+    const int r0 = tid >> 4, c4 = (tid & 15) * 4;
+    float ma[NL], mb[NL];
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+        const int rowa = ti * GF_T + r0 + 16 * q, rowb = tj * GF_T + r0 + 16 * q;
+        ma[q] = (mean && rowa < C) ? mean[rowa] : 0.f;
+        mb[q] = (mean && rowb < C) ? mean[rowb] : 0.f;
+    }
+    f32x4 ra[NL], rb[NL];
+    auto load_stage = [&](int p0) {
+        const int pp = p0 + c4;
+        const unsigned m = gf_mask4(pp, p_end);  // decided before any address
+        const int y = pp / W, x = pp - y * W;
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int rowa = ti * GF_T + r0 + 16 * q, rowb = tj * GF_T + r0 + 16 * q;
+            ra[q] = gf_load4_mirror(f + (int64_t)min(rowa, C - 1) * HW, pp, rowa < C ? m : 0u, ma[q], kind, H, W, y, x);
+            rb[q] = gf_load4(f + (int64_t)min(rowb, C - 1) * HW, pp, rowb < C ? m : 0u, mb[q]);
+        }
+    };
+    auto store_stage = [&]() {
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            *reinterpret_cast<f32x4*>(At + (r0 + 16 * q) * GF_RS + c4) = ra[q];
+            *reinterpret_cast<f32x4*>(Bt + (r0 + 16 * q) * GF_RS + c4) = rb[q];
+        }
+    };
+
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+
+    if (p_begin < p_end) {  // workgroup-uniform
+        load_stage(p_begin);
+        for (int p0 = p_begin; p0 < p_end; p0 += GF_K) {
+            __syncthreads();  // previous stage fully consumed
+            store_stage();
+            __syncthreads();
+            if (p0 + GF_K < p_end) load_stage(p0 + GF_K);
+            if (ti == tj && wi > wj) continue;  // (wave-uniform) the block below the diagonal of a diagonal tile is never read
+            const float* at = At + (wi * 32 + i32) * GF_RS + 4 * half;
+            const float* bt = Bt + (wj * 32 + i32) * GF_RS + 4 * half;
+#pragma unroll
+            for (int q = 0; q < GF_K / 8; ++q) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(at + 8 * q);
+                const f32x4 b = *reinterpret_cast<const f32x4*>(bt + 8 * q);
+#pragma unroll
+                for (int cp = 0; cp < 4; ++cp) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cp], b[cp], acc, 0, 0, 0);
+            }
+        }
+    }
+    float* out = partial + (((int64_t)s * npairs + blockIdx.x) * ksplit + ks) * (GF_T * GF_T);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        out[row * GF_T + wj * 32 + i32] = acc[r];
+    }
+}
+
+// grid (tile pairs, 16, M): every thread owns one element of the 64x64 tile, adds its slab values in index order (fp64), applies the mirror's
+// scale and writes the element and its transpose; in a diagonal tile the threads with er <= ec only.
+__global__ void __launch_bounds__(256)
+gf_finish_kernel(const float* __restrict__ partial, float* __restrict__ gram, GfMirrors mr, int C, int npairs, int ksplit) {
+    const int s = blockIdx.z;
+    const int ntile = (C + GF_T - 1) / GF_T;
+    int ti, tj;
+    gf_pair(blockIdx.x, ntile, &ti, &tj);
+    const int e = blockIdx.y * 256 + threadIdx.x;
+    const int er = e / GF_T, ec = e % GF_T;
+    const int gi = ti * GF_T + er, gj = tj * GF_T + ec;
+    if (gi >= C || gj >= C || (ti == tj && er > ec)) return;
+    const float* base = partial + ((int64_t)s * npairs + blockIdx.x) * ksplit * (GF_T * GF_T) + e;
+    double sd = 0.0;
+    int k = 0;
+    for (; k + 15 < ksplit; k += 16) {  // sixteen loads in flight, the additions in the order of a plain loop
+        float v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = base[(int64_t)(k + u) * (GF_T * GF_T)];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) sd += (double)v[u];
+    }
+    for (; k < ksplit; ++k) sd += (double)base[(int64_t)k * (GF_T * GF_T)];
+    const float g = (float)(sd * mr.factor[s]);
+    float* gm = gram + (int64_t)s * C * C;
+    gm[(int64_t)gi * C + gj] = g;
+    gm[(int64_t)gj * C + gi] = g;
+}
+
+// Backward.  Workgroup = 64 output channels x 256 pixels, wave = 64 x 64 (2 x 2 accumulators), 32 input channels per LDS stage,
+// double-buffered (80 KB); the stages run over (mirror, channel block).  A mirror whose coef is 0 is left out.
+constexpr int GFB_KC = 32, GFB_PX = 256, GFB_CO = 64;
+
+template <bool ACC>
+__global__ void __launch_bounds__(256)
+gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ gx, GfMirrors mr, int M,
+              int C, int H, int W) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f32[];  // 2 x (Xl[32][256] + Wl[32][64])
+    float* smem = smem_f32;
+    constexpr int BUF = GFB_KC * GFB_PX + GFB_KC * GFB_CO;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 31, half = lane >> 5;
+    const int HW = H * W;
+    const int p0 = blockIdx.x * GFB_PX;
+    const int co0 = blockIdx.y * GFB_CO;
+    const int pq = p0 + 4 * (tid & 63);  // this thread's pixel quad in every stage (each wave's 64 lanes cover the 256 pixels)
+    const unsigned mq = gf_mask4(pq, HW);  // from indices alone; sigma(q) lies inside F exactly when q does
+    const int qy = pq / W, qx = pq - qy * W;
+
+    unsigned active = 0;
+    for (int s = 0; s < M; ++s)
+        if (mr.factor[s] != 0.0) active |= 1u << s;
+
+    f32x4 rx[8], rw[2];
+    auto load_stage = [&](int s, int k0) {
+        const int kind = mr.kind[s];
+        const float cf = (float)mr.factor[s];
+        const float* dr = d + (int64_t)s * C * C;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int row = k0 + (tid >> 6) + 4 * i;  // quad index tid + 256 i: 32 rows x 64 quads
+            const bool in = row < C;
+            rx[i] = gf_load4_mirror(f + (int64_t)(in ? row : 0) * HW, pq, in ? mq : 0u, (mean && in) ? mean[row] : 0.f, kind, H, W, qy, qx) * cf;
+        }
+        // Wl[k][co] = D[co0 + co][k0 + k] + D[k0 + k][co0 + co]: this thread holds (co, k .. k + 3) - a quad along k of the row co, and four
+        // elements of the column co, which a wave's 64 lanes (64 consecutive co) read as whole lines
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + 256 * i;  // 64 rows x 8 quads
+            const int co = co0 + (e & 63), kq = k0 + 4 * (e >> 6);
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (co < C) {
+                const float* drow = dr + (int64_t)co * C;
+                if (kq + 4 <= C) {
+                    v = *reinterpret_cast<const gf_f32x4u*>(drow + kq);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (kq + k < C) v[k] = drow[kq + k];
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (kq + k < C) v[k] += dr[(int64_t)(kq + k) * C + co];
+            }
+            rw[i] = v;
+        }
+    };
+    auto store_stage = [&](int buf) {
+        float* xl = smem + buf * BUF;
+        float* wl = xl + GFB_KC * GFB_PX;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(xl + (tid + 256 * i) * 4) = rx[i];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e = tid + 256 * i;  // a wave's lanes hold 64 different co: conflict-free LDS columns
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wl[(4 * (e >> 6) + k) * GFB_CO + (e & 63)] = rw[i][k];
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][u][r] = 0.f;
+
+    // the stage to load next: (mirror st, channel block k0); st == M: none left
+    int st = 0, k0 = 0;
+    while (st < M && !((active >> st) & 1u)) ++st;
+    auto advance = [&]() {
+        k0 += GFB_KC;
+        if (k0 >= C) {
+            k0 = 0;
+            ++st;
+            while (st < M && !((active >> st) & 1u)) ++st;
+        }
+    };
+    if (st < M) {  // workgroup-uniform, as every branch on st below
+        load_stage(st, k0);
+        store_stage(0);
+        advance();
+        __syncthreads();
+        int cur = 0;
+        while (true) {
+            const bool more = st < M;
+            if (more) load_stage(st, k0);
+            const float* xl = smem + cur * BUF;
+            const float* wl = xl + GFB_KC * GFB_PX;
+#pragma unroll
+            for (int kp = 0; kp < GFB_KC / 2; ++kp) {
+                const int kk = 2 * kp + half;
+                float a[2], b[2];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) a[t] = wl[kk * GFB_CO + t * 32 + j];
+#pragma unroll
+                for (int u = 0; u < 2; ++u) b[u] = xl[kk * GFB_PX + (wave * 2 + u) * 32 + j];
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b[u], acc[t][u], 0, 0, 0);
+            }
+            if (more) {
+                store_stage(cur ^ 1);
+                advance();
+            }
+            __syncthreads();
+            if (!more) break;
+            cur ^= 1;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int pix = p0 + (wave * 2 + u) * 32 + j;
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            // read-modify-write in two sweeps: all loads of the 16 registers first, then all stores (gram_bwd_kernel)
+            float prev[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
+                const bool ok = pix < HW && co < C;
+                prev[q] = 0.f;
+                if constexpr (ACC) prev[q] = gx[ok ? (int64_t)co * HW + pix : 0];
+            }
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
+                if (pix < HW && co < C) gx[(int64_t)co * HW + pix] = acc[t][u][q] + prev[q];
+            }
+        }
+    }
+}
+
+// slabs per (mirror, tile pair) and their length in pixels: about 768 workgroups per mirror's matrix, slices of whole stages - a function of
+// (C, H W) alone
+static void gf_plan(int c, int64_t hw, int* npairs, int* ksplit, int* chunk) {
+    const int ntile = (c + GF_T - 1) / GF_T;
+    *npairs = ntile * (ntile + 1) / 2;
+    const int64_t stages = (hw + GF_K - 1) / GF_K;
+    int64_t want = (768 + *npairs - 1) / *npairs;
+    if (want > GF_KMAX) want = GF_KMAX;
+    if (want > stages) want = stages;
+    if (want < 1) want = 1;
+    const int64_t ch = ((hw + want - 1) / want + GF_K - 1) / GF_K * GF_K;
+    *chunk = (int)ch;
+    *ksplit = (int)((hw + ch - 1) / ch);
+}
+
+static bool gf_shape_ok(int mirrors, int c, int h, int w) {
+    return mirrors >= 1 && mirrors <= GF_MMAX && c >= 1 && c <= (1 << 16) && h >= 1 && w >= 1 && (int64_t)h * w < (1ll << 30);
+}
+
+// the host arrays of a call into a launch argument; 0, or the error code after set_error
+static int gf_pack(const char* who, const int* kinds, const double* factors, int mirrors, GfMirrors* out) {
+    for (int s = 0; s < GF_MMAX; ++s) {
+        out->kind[s] = 0;
+        out->factor[s] = 0.0;
+    }
+    for (int s = 0; s < mirrors; ++s) {
+        MAUA_REQUIRE(kinds[s] >= 0 && kinds[s] <= 2, MAUA_E_UNSUPPORTED, "%s: kind %d of mirror %d (0 = LR, 1 = UD, 2 = point mirror)", who,
+                     kinds[s], s);
+        out->kind[s] = kinds[s];
+        out->factor[s] = factors[s];
+    }
+    return MAUA_OK;
+}
+
+}  // namespace maua
+
+using namespace maua;
+
+extern "C" {
+
+int maua_gram_flip_supported(int mirrors, int c, int h, int w) { return gf_shape_ok(mirrors, c, h, w) ? 1 : 0; }
+
+size_t maua_gram_flip_workspace_bytes(int mirrors, int c, int h, int w) {
+    if (!gf_shape_ok(mirrors, c, h, w)) return 0;
+    int npairs, ksplit, chunk;
+    gf_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
+    return (size_t)mirrors * npairs * ksplit * GF_T * GF_T * sizeof(float);
+}
+
+int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c, int h, int w,
+                       void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    MAUA_REQUIRE(f && kinds && scales && gram && workspace, MAUA_E_INVAL, "gram_flip_fwd: null pointer");
+    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "gram_flip_fwd: %d mirrors (1 .. %d), %d channels, %d x %d pixels", mirrors,
+                 GF_MMAX, c, h, w);
+    GfMirrors mr;
+    int rc = gf_pack("gram_flip_fwd", kinds, scales, mirrors, &mr);
+    if (rc) return rc;
+    const size_t need = maua_gram_flip_workspace_bytes(mirrors, c, h, w);
+    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "gram_flip_fwd: workspace %zu < %zu", workspace_bytes, need);
+    int npairs, ksplit, chunk;
+    gf_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(gf_partial_kernel, dim3(npairs, ksplit, mirrors), dim3(256), 0, s, f, mean, (float*)workspace, mr, c, h, w, npairs, ksplit,
+                       chunk);
+    rc = check_launch("gf_partial_kernel");
+    if (rc) return rc;
+    hipLaunchKernelGGL(gf_finish_kernel, dim3(npairs, GF_T * GF_T / 256, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, c, npairs,
+                       ksplit);
+    return check_launch("gf_finish_kernel");
+}
+
+int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
+                       int h, int w, int accumulate, maua_stream_t stream) {
+    MAUA_REQUIRE(d && f && kinds && coefs && gx, MAUA_E_INVAL, "gram_flip_bwd: null pointer");
+    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "gram_flip_bwd: %d mirrors (1 .. %d), %d channels, %d x %d pixels", mirrors,
+                 GF_MMAX, c, h, w);
+    GfMirrors mr;
+    const int rc = gf_pack("gram_flip_bwd", kinds, coefs, mirrors, &mr);
+    if (rc) return rc;
+    const int64_t hw = (int64_t)h * w;
+    constexpr size_t lds = 2ull * (GFB_KC * GFB_PX + GFB_KC * GFB_CO) * sizeof(float);
+    const dim3 grid((unsigned)((hw + GFB_PX - 1) / GFB_PX), (unsigned)((c + GFB_CO - 1) / GFB_CO));
+    auto launch = [&](auto kernel) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, gx, mr, mirrors, c, h, w);
+    };
+    if (accumulate) launch(gf_bwd_kernel<true>);
+    else launch(gf_bwd_kernel<false>);
+    return check_launch("gf_bwd_kernel");
+}
+
+}  // extern "C"

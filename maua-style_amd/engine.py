@@ -104,6 +104,8 @@ class StyleEngine:
                     raise UnsupportedNet("guided StyleLoss runs on the module path")
                 if m.shift_factor > 0:
                     raise UnsupportedNet("shifted StyleLoss runs on the module path")
+                if m.mirror_kinds():
+                    raise UnsupportedNet("mirrored StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -461,6 +463,8 @@ class StyleEngine:
                         or w.shape[1] not in (1, shapes_src[1]):
                     raise UnsupportedNet("weighted ContentLoss of this shape runs on the module path")
             return True
+        if m.mirror_kinds():  # (set after the plan was made: no engine evaluation without the mirror terms)
+            raise UnsupportedNet("mirrored StyleLoss runs on the module path")
         if getattr(m, "guide", None) is not None:
             gd = getattr(self, "guided", {}).get(id(s)) if plan.on("guided_engine") else None
             if gd is None:  # (planner field guided_engine off, or guides set after the plan was made)

@@ -79,6 +79,10 @@ SIGNATURES = {
     "maua_gram_shift_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "maua_gram_shift_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "maua_gram_shift_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_gram_flip_supported": (c_i, [c_i, c_i, c_i, c_i]),
+    "maua_gram_flip_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "maua_gram_flip_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_gram_flip_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
@@ -959,6 +963,53 @@ def gram_shift_bwd(d, f, shifts, coefs, mean, gx, accumulate):
     axes, deltas, fac = _shift_args(shifts, coefs)
     _check(lib().maua_gram_shift_bwd(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), axes, deltas, fac, _ptr(_f32(gx, "gx")),
                                      n, c, h, w, int(accumulate), _stream()), "maua_gram_shift_bwd")
+    return gx
+
+
+def gram_flip_supported(mirrors, c, h, w):
+    return bool(lib().maua_gram_flip_supported(int(mirrors), int(c), int(h), int(w)))
+
+
+def gram_flip_workspace_bytes(mirrors, c, h, w):
+    return lib().maua_gram_flip_workspace_bytes(int(mirrors), int(c), int(h), int(w))
+
+
+def _flip_args(kinds, factors):
+    """kinds: [0 = LR | 1 = UD | 2 = point mirror, ...] -> the two host arrays of the gram_flip entry points."""
+    n = len(kinds)
+    if n != len(factors):
+        raise HipError(f"{n} mirrors and {len(factors)} factors")
+    return (ctypes.c_int * n)(*[int(k) for k in kinds]), (ctypes.c_double * n)(*[float(v) for v in factors])
+
+
+def gram_flip_fwd(f, kinds, scales, mean=None, out=None, workspace=None):
+    """f: (1,C,H,W) or (C,H,W); kinds: [0 = LR | 1 = UD | 2 = point mirror, ...]; scales: one float per mirror; mean: (C,) row means to
+    subtract or None.  Returns grams (M,C,C), gram[m][c][k] = scales[m] sum_p X[c][sigma_m(p)] X[k][p] over all pixels (bit-symmetric)."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    if f.numel() != c * h * w or (mean is not None and mean.numel() != c):
+        raise HipError("gram_flip_fwd: f is one (C, H, W) map and mean holds C values")
+    n = len(kinds)
+    kd, fac = _flip_args(kinds, scales)
+    if out is None:
+        out = torch.empty(n, c, c, device=f.device, dtype=torch.float32)
+    elif out.numel() != n * c * c:
+        raise HipError("gram_flip_fwd: out is (M, C, C)")
+    workspace = _ws(workspace, gram_flip_workspace_bytes(n, c, h, w), f.device)
+    _check(lib().maua_gram_flip_fwd(_ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), kd, fac, _ptr(_f32(out, "out")), n, c, h, w,
+                                    workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()), "maua_gram_flip_fwd")
+    return out
+
+
+def gram_flip_bwd(d, f, kinds, coefs, mean, gx, accumulate):
+    """gx (+)= sum_m coefs[m] (d[m] + d[m]^T) X mirrored by sigma_m, X = f - mean; d: (M,C,C) as given (not symmetrised).  The gradient with
+    respect to f in the covariance form too: the term through the row means vanishes."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(kinds)
+    if f.numel() != c * h * w or d.numel() != n * c * c or gx.numel() != f.numel() or (mean is not None and mean.numel() != c):
+        raise HipError("gram_flip_bwd: shapes of d, f, mean and gx do not agree")
+    kd, fac = _flip_args(kinds, coefs)
+    _check(lib().maua_gram_flip_bwd(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), kd, fac, _ptr(_f32(gx, "gx")),
+                                    n, c, h, w, int(accumulate), _stream()), "maua_gram_flip_bwd")
     return gx
 
 

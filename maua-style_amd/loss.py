@@ -16,6 +16,10 @@ field guided_engine is on (then engine.StyleEngine evaluates it; targets are sti
 
 Long-range consistency (--shift_factor; Berger & Memisevic 2016): with `shift_factor > 0` a StyleLoss also matches the products of the
 activation with translated copies of itself (csrc/gram_shift.hip).  Such a network runs through these modules only.
+
+Symmetry (the same paper's other half): with `flip_factor > 0` a StyleLoss also matches the products of the activation with its left-right
+and its up-down mirror image, with `rotation_factor > 0` the product with its point mirror (rotation by 180 degrees; csrc/gram_flip.hip,
+DESIGN.md section 13).  Module path only, like the shift terms.
 """
 import sys
 
@@ -170,6 +174,41 @@ class _ShiftGramFn(torch.autograd.Function):
         return gx, None, None, None
 
 
+MIRROR_LR, MIRROR_UD, MIRROR_180 = 0, 1, 2  # the kinds of csrc/gram_flip.hip
+
+
+class _FlipGramFn(torch.autograd.Function):
+    """G_m[c][k] = scale_m sum_p X[c][sigma_m(p)] X[k][p] for the mirrors `kinds` (0 = LR, 1 = UD, 2 = point mirror) of one frame x
+    (1, C, H, W), over all pixels, X = x - mu (mu: the map's row means in the covariance form, else 0); scale_m = 1 / (C H W) where `scales` is
+    None (apply takes all four arguments).  Symmetric, bit for bit.  Backward: hip.gram_flip_bwd alone - a mirror permutes the pixels, so the
+    centred rows still sum to zero and the term through the means vanishes."""
+
+    @staticmethod
+    def forward(ctx, x, kinds, use_covariance, scales):
+        B, C, H, W = x.shape
+        if B != 1:
+            raise ValueError("mirrored Gram matrices: one frame per call (B = 1)")
+        kinds = [int(k) for k in kinds]
+        if scales is None:
+            scales = [1.0 / (C * H * W)] * len(kinds)
+        xc = x.contiguous()
+        mean = None
+        if use_covariance:
+            mean = torch.empty(C, device=x.device, dtype=torch.float32)
+            hip.gram_row_means(xc, mean, hip._ws(None, hip.gram_workspace_bytes(C, H * W), x.device))
+        grams = hip.gram_flip_fwd(xc, kinds, scales, mean)
+        ctx.save_for_backward(xc)
+        ctx.mean, ctx.kinds, ctx.scales = mean, kinds, list(scales)
+        return grams
+
+    @staticmethod
+    def backward(ctx, g):
+        (xc,) = ctx.saved_tensors
+        gx = torch.empty_like(xc)
+        hip.gram_flip_bwd(g.contiguous(), xc, ctx.kinds, ctx.scales, ctx.mean, gx, False)
+        return gx, None, None, None
+
+
 class LayerGuides:
     """The guides of one style layer: `g` (R, H_l W_l) = the image-resolution guides resized to the activation with the project's bilinear
     kernel, `mass` N_r = sum g_r^2 (device, fp64; `mass_host` its one read-back), `active` = [N_r >= 1] and `scale` = 1 / (C N_r) on the
@@ -242,10 +281,19 @@ class GramMatrix(nn.Module):
     """(B*C) x (B*C) Gram matrix of a feature batch, or its covariance form (reference loss.py:67-91).  With exactly one of
     `shift_x` / `shift_y` nonzero (one frame, B = 1): the raw shifted product X_A X_B^T of the map with itself translated by that many
     pixels along the axis, X_A[c] = X[c] at p + offset, X_B[k] = X[k] at p, over the pairs inside the map (not symmetric; X is centred on
-    the whole map's row means in the covariance form).  The reference's own code for these arguments always ends with y = x (and its
-    `::-1` slices are illegal in torch); `shift_t` and the flip arguments are accepted and have no effect."""
+    the whole map's row means in the covariance form).  With `flip_h` (one frame): the raw product of the map's left-right mirror image
+    with the map, sum_p X[c][sigma(p)] X[k][p] over all pixels; `flip_v`: the up-down mirror; both: the point mirror (rotation by 180
+    degrees).  These are symmetric.  A flip together with a shift raises.  The reference's own code for these arguments always ends with
+    y = x (and its `::-1` slices are illegal in torch); `shift_t` is accepted and has no effect."""
 
     def forward(self, x, shift_x=0, shift_y=0, shift_t=0, flip_h=False, flip_v=False, use_covariance=False):
+        if flip_h or flip_v:
+            if shift_x or shift_y:
+                raise ValueError("GramMatrix: a flip and a shift together are not defined")
+            if x.shape[0] != 1:
+                raise ValueError("GramMatrix: a mirrored product needs one frame (B = 1)")
+            kind = MIRROR_180 if flip_h and flip_v else MIRROR_LR if flip_h else MIRROR_UD
+            return _FlipGramFn.apply(x, [kind], use_covariance, [1.0])[0]
         if shift_x or shift_y:
             if shift_x and shift_y:
                 raise ValueError("GramMatrix: one of shift_x / shift_y at a time")
@@ -258,7 +306,12 @@ class GramMatrix(nn.Module):
 
 class StyleLoss(nn.Module):
     """Gram-matrix MSE against blended style targets (reference loss.py:94-186): a per-frame 'static' term
-    and, when video_style_factor > 0 (the default, 100), a whole-batch 'dynamic' term."""
+    and, when video_style_factor > 0 (the default, 100), a whole-batch 'dynamic' term.
+
+    Per frame the static scalar t = mse(G, T) becomes t + shift_factor sum_s mse(G_s, T_s) + flip_factor (mse(G_LR, T_LR) + mse(G_UD, T_UD))
+    + rotation_factor mse(G_180, T_180): the shifted products of DESIGN.md section 12 and the mirrored ones of section 13.  `rotation_factor`
+    drives the 180 degree term only; the paper's 90 degree terms (square maps, a transposing read) are not implemented.  The dynamic term
+    gets neither."""
 
     def __init__(self, strength, use_covariance=False, normalize=False, video_style_factor=0, shift_factor=0,
                  flip_factor=0, rotation_factor=0):
@@ -287,6 +340,7 @@ class StyleLoss(nn.Module):
         self.shift_target_deltas = None  # the deltas every capture pass so far produced (None: nothing captured)
         self._shift_dropped = set()  # deltas some capture pass produced and another did not
         self._shift_named = set()
+        self.flip_targets = {}  # mirror kind (0 = LR, 1 = UD, 2 = point mirror) -> (C, C): sum of blend weight x mirrored Gram
         self.guided_target = None  # (R, C, C): sum over the style images of blend weight x guided Gram, per region
         self.guided_weight = None  # R blend-weight sums over the style images in which the region is active
         self._guided_ready = None
@@ -366,6 +420,8 @@ class StyleLoss(nn.Module):
         if self._guide is not None:
             if self.shift_factor > 0:
                 raise NotImplementedError("StyleLoss: guides and shift_factor > 0 together are not implemented")
+            if self.flip_factor > 0 or self.rotation_factor > 0:
+                raise NotImplementedError("StyleLoss: guides and flip_factor / rotation_factor > 0 together are not implemented")
             self.guided_loss(input)
             return input
         self.static_loss(input)
@@ -391,9 +447,13 @@ class StyleLoss(nn.Module):
                 t = self.crit(gram, self.target)
                 if self.shift_factor > 0:
                     t = self._shift_terms(frame, t)
+                if self.mirror_kinds():
+                    t = self._flip_terms(frame, t)
                 self.loss += self._accumulate(t) * self.strength / frames
             if self.mode == "capture" and self.shift_factor > 0:
                 self._shift_capture(frame, frames)
+            if self.mode == "capture" and self.mirror_kinds():
+                self._flip_capture(frame, frames)
 
     # -- long-range consistency (shift_factor > 0): G_s of loss.shift_deltas(H, W) along x and y, matched like the static Gram matrix
     def _shift_grams(self, frame, deltas):
@@ -440,6 +500,29 @@ class StyleLoss(nn.Module):
         for i, d in enumerate(use):
             at = self.shift_target_deltas.index(d)
             t = t + self.shift_factor * (self.crit(grams[2 * i], self.shift_targets_x[at]) + self.crit(grams[2 * i + 1], self.shift_targets_y[at]))
+        return t
+
+    # -- symmetry (flip_factor, rotation_factor > 0): G_m of the mirrors in use, matched like the static Gram matrix
+    def mirror_kinds(self):
+        """The mirror kinds in use: LR and UD with flip_factor > 0, the point mirror with rotation_factor > 0."""
+        return ([MIRROR_LR, MIRROR_UD] if self.flip_factor > 0 else []) + ([MIRROR_180] if self.rotation_factor > 0 else [])
+
+    def _flip_capture(self, frame, frames):
+        kinds = self.mirror_kinds()
+        grams = _FlipGramFn.apply(frame, kinds, bool(self.use_covariance), None).detach()
+        for i, kind in enumerate(kinds):
+            contrib = self.blend_weight * grams[i] / frames
+            self.flip_targets[kind] = contrib if kind not in self.flip_targets else self.flip_targets[kind] + contrib
+
+    def _flip_terms(self, frame, t):
+        kinds = self.mirror_kinds()
+        missing = [k for k in kinds if k not in self.flip_targets]
+        if missing:
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: mirror targets not captured (kinds {missing})")
+        grams = _FlipGramFn.apply(frame, kinds, bool(self.use_covariance), None)
+        for i, kind in enumerate(kinds):
+            factor = self.rotation_factor if kind == MIRROR_180 else self.flip_factor
+            t = t + factor * self.crit(grams[i], self.flip_targets[kind])
         return t
 
     def dynamic_loss(self, input):

@@ -769,7 +769,9 @@ def assemble(features, layer_list, args):
             if args.verbose:
                 print("Setting up style layer " + str(index) + ": " + str(layer_name))
             add(StyleLoss(args.style_weight, args.use_covariance, args.normalize_gradients,
-                          video_style_factor=args.video_style_factor, shift_factor=args.shift_factor),
+                          video_style_factor=args.video_style_factor, shift_factor=args.shift_factor,
+                          # preset keys (--load_args), not flags: the reference's flag surface has neither
+                          flip_factor=float(getattr(args, "flip_factor", 0) or 0), rotation_factor=float(getattr(args, "rotation_factor", 0) or 0)),
                 "style", style_losses)
             found_style = True
         return found_content, found_style

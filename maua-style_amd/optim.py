@@ -58,9 +58,18 @@ def _shifted(net_or_losses):
     return any(isinstance(m, loss_mod.StyleLoss) and m.shift_factor > 0 for m in mods)
 
 
+def _mirrored(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) have flip_factor > 0 or rotation_factor > 0?  Such a network runs on
+    the module path, like a shifted one."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(isinstance(m, loss_mod.StyleLoss) and bool(m.mirror_kinds()) for m in mods)
+
+
 def _style_targets_missing(net):
-    """A style module without its target - or, with shift_factor > 0, without its shift targets (the factor was set after the capture)."""
-    return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None) for m in net.style_losses)
+    """A style module without its target - or, with shift_factor > 0, without its shift targets, or with a mirror in use without that
+    mirror's target (the factor was set after the capture)."""
+    return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None)
+               or any(k not in m.flip_targets for k in m.mirror_kinds()) for m in net.style_losses)
 
 
 def _engine_of(net):
@@ -69,6 +78,8 @@ def _engine_of(net):
         return None  # (not remembered: the same network without guides takes the engine again)
     if _shifted(net):
         return None  # (not remembered either: the same network with shift_factor 0 takes the engine again)
+    if _mirrored(net):
+        return None  # (nor this: with flip_factor and rotation_factor back at 0 the network takes the engine again)
     eng = getattr(net, "_maua_engine", None)
     if eng is None and not getattr(net, "_maua_engine_refused", False):
         if not all(hasattr(net, a) for a in ("content_losses", "style_losses", "tv_losses", "temporal_losses")):
@@ -209,6 +220,8 @@ class PixelOptimizer:
                 raise engine_mod.UnsupportedNet("guided StyleLoss runs on the module path")
             if _shifted(losses):
                 raise engine_mod.UnsupportedNet("shifted StyleLoss runs on the module path")
+            if _mirrored(losses):
+                raise engine_mod.UnsupportedNet("mirrored StyleLoss runs on the module path")
             self.engine = getattr(net, "_maua_engine", None) or engine_mod.StyleEngine(net, losses)
             net._maua_engine = self.engine
         except engine_mod.UnsupportedNet:

@@ -1,0 +1,171 @@
+"""Cost of the mirrored Gram kernels (csrc/gram_flip.hip) on one MI355X, beside the plain Gram kernels and one x-shift on the same tensors,
+and of a flip_factor job beside the same job without the term.
+
+Kernels: the five VGG-19 style-layer shapes of a 1024 x 1024 image (C x H_l x W_l).  Per shape, forward and backward of
+  base           hip.gram_fwd / hip.gram_bwd (the kernels every job runs: the baseline, never the new code);
+  x4             hip.gram_shift_fwd / hip.gram_shift_bwd with one shift, delta 4 along x: the yardstick of the expectation below;
+  LR / UD / 180  one mirror alone;
+  LR+UD          the two mirrors of flip_factor in one call (what a StyleLoss with flip_factor > 0 and rotation_factor 0 launches);
+  all3           the three mirrors in one call.
+The expectation: a mirror reads the bytes one shift reads, computes the tile pairs on or above the diagonal only and has one run of
+backward stages where a shift has two, so it should not cost more than x4 of the same run and shape (`x x4` <= 1).
+The variants run interleaved, `--rounds` rounds of `--reps` back-to-back calls between device events after a warm-up round; the table gives
+the median and the minimum over the rounds.  Feature maps are relu(randn): the same data for every variant of a shape.
+
+Job: VGG-19 (seeded synthetic weights), 1024 x 1024, default layers, L-BFGS: iterations per second of `--steps` steps after `--warmup` (host
+clock around a device synchronise) with flip_factor 0 on the fused engine (the project's normal route), flip_factor 0 on the module path
+(autograd over the HIP kernels) and flip_factor 1, rotation_factor 0 (module path: the only route of the mirror terms).
+
+    python tools/bench_flip.py [--rounds 7] [--reps 10] [--steps 20] [--warmup 3] [--size 1024] > profiles/bench_flip.md
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "maua-style_amd")]
+
+LR, UD, ROT180 = 0, 1, 2
+
+
+def layer_shapes(size):
+    return [("relu1_1", 64, size, size), ("relu2_1", 128, size // 2, size // 2), ("relu3_1", 256, size // 4, size // 4),
+            ("relu4_1", 512, size // 8, size // 8), ("relu5_1", 512, size // 16, size // 16)]
+
+
+def kernel_table(a, out):
+    import hip
+    import loss
+    out.append("| layer | C x H x W | variant | matrices | forward us (median / min) | x base | x x4 | backward us (median / min) | x base | x x4 |")
+    out.append("|---|---|---|---|---|---|---|---|---|---|")
+    dearer = []  # a mirror alone that costs more than the x-shift of the same run and shape
+    for name, C, H, W in layer_shapes(a.size):
+        N = H * W
+        gen = torch.Generator().manual_seed(C + H)
+        f = torch.relu(torch.randn(C, H, W, generator=gen)).cuda()
+        d1 = torch.randn(C, C, generator=gen).cuda()
+        dsym = (d1 + d1.t()).contiguous()
+        gf = torch.empty(C, H, W, device="cuda")
+        ws_b = torch.empty(hip.gram_workspace_bytes(C, N), dtype=torch.uint8, device="cuda")
+        gram_b = torch.empty(C, C, device="cuda")
+        variants = {"base": (0, lambda: hip.gram_fwd(f, 1.0 / (C * N), False, out=gram_b, workspace=ws_b),
+                             lambda: hip.gram_bwd(dsym, f, None, gf, False, workspace=ws_b))}
+        shift, sscale = [(0, 4)], [1.0 / (C * loss.shift_pairs(0, 4, H, W))]
+        ws_s = torch.empty(hip.gram_shift_workspace_bytes(1, C, H, W), dtype=torch.uint8, device="cuda")
+        gram_s = torch.empty(1, C, C, device="cuda")
+        ds = d1.expand(1, C, C).contiguous()
+        variants["x4"] = (1, lambda: hip.gram_shift_fwd(f, shift, sscale, None, out=gram_s, workspace=ws_s),
+                          lambda: hip.gram_shift_bwd(ds, f, shift, sscale, None, gf, False))
+        keep = []
+        for label, kinds in (("LR", [LR]), ("UD", [UD]), ("180", [ROT180]), ("LR+UD", [LR, UD]), ("all3", [LR, UD, ROT180])):
+            M = len(kinds)
+            scales = [1.0 / (C * N)] * M
+            ws = torch.empty(hip.gram_flip_workspace_bytes(M, C, H, W), dtype=torch.uint8, device="cuda")
+            grams = torch.empty(M, C, C, device="cuda")
+            d = d1.expand(M, C, C).contiguous()
+            keep.append((ws, grams, d))
+            variants[label] = (M, lambda kinds=kinds, scales=scales, ws=ws, grams=grams: hip.gram_flip_fwd(f, kinds, scales, None, out=grams, workspace=ws),
+                               lambda kinds=kinds, scales=scales, d=d: hip.gram_flip_bwd(d, f, kinds, scales, None, gf, False))
+        times = {k: ([], []) for k in variants}
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for rnd in range(a.rounds + 1):  # round 0 warms up
+            for k, (_, *fns) in variants.items():
+                for which, fn in enumerate(fns):
+                    fn()
+                    ev[0].record()
+                    for _ in range(a.reps):
+                        fn()
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    if rnd:
+                        times[k][which].append(ev[0].elapsed_time(ev[1]) / a.reps * 1e3)
+        med = {k: [statistics.median(t) for t in v] for k, v in times.items()}
+        for k, v in times.items():
+            out.append(f"| {name} | {C} x {H} x {W} | {k} | {variants[k][0] or '-'} | {med[k][0]:.1f} / {min(v[0]):.1f} | {med[k][0] / med['base'][0]:.2f} | "
+                       f"{med[k][0] / med['x4'][0]:.2f} | {med[k][1]:.1f} / {min(v[1]):.1f} | {med[k][1] / med['base'][1]:.2f} | "
+                       f"{med[k][1] / med['x4'][1]:.2f} |")
+            print(json.dumps(dict(layer=name, C=C, H=H, W=W, variant=k, matrices=variants[k][0], fwd_us=med[k][0], bwd_us=med[k][1],
+                                  fwd_min_us=min(v[0]), bwd_min_us=min(v[1]))), file=sys.stderr, flush=True)
+            if variants[k][0] == 1 and k != "x4":
+                dearer += [f"{name} {k} {way} {med[k][i] / med['x4'][i]:.2f}" for i, way in enumerate(("forward", "backward"))
+                           if med[k][i] > med["x4"][i]]
+        del keep
+    out += ["", "Expectation (a mirror alone costs no more than the x-shift of the same run and shape): "
+            + ("holds for every layer, kind and direction." if not dearer else "MISSED by " + "; ".join(dearer) + ".")]
+
+
+def job_rates(a, out):
+    import config
+    import models
+    import optim
+    import synth
+    tmp = tempfile.mkdtemp(prefix="bench_flip_")
+    wfile = os.path.join(tmp, "vgg19_synth.pth")
+    torch.save(synth.vgg19_state_dict(), wfile)
+    scaling = os.path.join(tmp, "scaling.json")
+    with open(scaling, "w") as fh:
+        json.dump({"100000": {"gpu": "0", "multidevice": False}}, fh)
+    S = a.size
+    content, style, init = synth.images(S)
+    rates = {}
+    for label, ff in (("flip_factor 0, fused engine", 0.0), ("flip_factor 0, module path", 0.0), ("flip_factor 1, rotation_factor 0 (module path)", 1.0)):
+        preset = os.path.join(tmp, "sym.json")
+        with open(preset, "w") as fh:
+            json.dump({"flip_factor": ff, "rotation_factor": 0.0}, fh)
+        args = config.get_args(["--content", "c.png", "--style", "s.png", "--model_file", wfile, "--disable_check", "--scaling_args", scaling,
+                                "--image_sizes", str(S), "--num_iters", str(a.steps), "--seed", "0", "--no_hist_match", "--load_args", preset])
+        optim.set_model_args(args, S)
+        net, losses = models.load_model(args)
+        optim.set_content_targets(net, content, args)
+        optim.set_style_targets(net, [style], args)
+        for m in losses:
+            m.mode = "loss"
+        opt = optim.PixelOptimizer(net, losses, init, args, planned_iters=a.steps + a.warmup)
+        if "module path" in label:
+            opt.engine = None
+        assert (opt.engine is not None) == ("fused" in label), label
+        for _ in range(a.warmup):
+            opt.step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            opt.step()
+        torch.cuda.synchronize()
+        rates[label] = a.steps / (time.perf_counter() - t0)
+        print(json.dumps(dict(job=label, size=S, steps=a.steps, iterations_per_s=rates[label])), file=sys.stderr, flush=True)
+        del opt, net, losses
+        torch.cuda.empty_cache()
+    out.append("| job | iterations/s | ms per iteration |")
+    out.append("|---|---|---|")
+    for k, v in rates.items():
+        out.append(f"| {k} | {v:.2f} | {1e3 / v:.2f} |")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--size", type=int, default=1024)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_flip: no GPU visible (there is no CPU fallback, and a CPU timing would say nothing)")
+    out = [f"# Mirrored Gram kernels and a flip_factor job at {a.size} x {a.size} (tools/bench_flip.py)", "",
+           f"Device: {torch.cuda.get_device_name(0)}.  Kernel times: median / minimum over {a.rounds} interleaved rounds of {a.reps} calls, device events.",
+           "`x base` = median over the median of hip.gram_fwd / hip.gram_bwd on the same tensor, `x x4` = over the median of one x-shift by 4 "
+           "(hip.gram_shift_fwd / hip.gram_shift_bwd) in the same run; `matrices` = matrices per call.", ""]
+    kernel_table(a, out)
+    out += ["", f"## Whole job, L-BFGS, {a.steps} steps after {a.warmup}", ""]
+    job_rates(a, out)
+    print("\n".join(out))
+
+
+if __name__ == "__main__":
+    main()
