@@ -417,6 +417,41 @@ int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, cons
 int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
                        int h, int w, int accumulate, maua_stream_t stream);
 
+/* ---- shifted and mirrored Gram terms of the fused engine (gram_shift.hip, gram_flip.hip) ------------------------ */
+/* The two forward passes above with the MSE against per-term targets formed by their finishing launch, and the two backward passes with a
+ * ReLU mask in their epilogue.  Arguments, limits and return codes are those of maua_gram_shift_fwd / _bwd and maua_gram_flip_fwd / _bwd;
+ * the further pointers must not be null either (MAUA_E_INVAL), a record that does not fit returns MAUA_E_UNSUPPORTED - before any launch.
+ * maua_shift_gram_fwd_mse_ledger: maua_gram_shift_fwd (gram: the same bits - same slabs, same fixed-order fp64 fold) whose finishing
+ *   launch also writes
+ *     dmat[s][C][C] = grad_scales[s] * (gram[s] - target[s]), element by element (NOT symmetrised: gram[s] is not symmetric); exact zeros -
+ *       written, never left out - where grad_scales[s] == 0;
+ *     ONE ledger record for the call in `slot` of `ledger` (maua_loss_ledger_bytes): sum_s loss_scales[s] * sum (gram[s] - target[s])^2,
+ *       every partial sum weighted by its shift's loss_scale, the record's scale 1; a shift with loss_scales[s] == 0 contributes exact zeros.
+ *   target[shifts][C][C]; loss_scales, grad_scales: HOST arrays of `shifts` doubles like scales.  Deterministic: no float atomics, the same
+ *   inputs give the same bits.  workspace: maua_gram_shift_workspace_bytes, as for maua_gram_shift_fwd.
+ * maua_flip_gram_fwd_mse_ledger: the same for maua_gram_flip_fwd.  dmat[m] is formed on and above the diagonal and mirrored like gram[m]
+ *   (bit-symmetric; the target is read on and above its diagonal only); an element off the diagonal counts twice in the loss.
+ * maua_shift_gram_mse_ledger_supported, maua_flip_gram_mse_ledger_supported: 1 when the finishing launch's partial sums - 16, 8 or 4 per
+ *   (term, 64 x 64 tile pair): the most that fit, a function of (terms, C) alone - fit one record, nt = ceil(C / 64):
+ *     shifts * nt^2 * 4 <= 4096 (all tile pairs; VGG-19's 4 x 512 takes 16 per pair: 4096; 16 shifts: C <= 512),
+ *     mirrors * nt (nt + 1) / 2 * 4 <= 4096 (the pairs on or above the diagonal; VGG-19's 3 x 512 takes 16 per pair: 1728; 4 mirrors: C <= 1408).
+ * maua_shift_gram_bwd_masked, maua_flip_gram_bwd_masked: maua_gram_shift_bwd / maua_gram_flip_bwd with relu_mask[C][h w] (nullable): where
+ *   relu_mask <= 0 the element of gx is written as 0 (also with accumulate != 0: what was accumulated into is dropped - pre-masked
+ *   gradients, as maua_guided_gram_bwd_masked).  A null mask gives the bits of the plain entry point.  One launch, the mask is applied in
+ *   its epilogue. */
+int maua_shift_gram_mse_ledger_supported(int shifts, int c);
+int maua_shift_gram_fwd_mse_ledger(const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram,
+                                   int shifts, int c, int h, int w, const float* target, const double* loss_scales, const double* grad_scales,
+                                   float* dmat, double* ledger, int slot, void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_shift_gram_bwd_masked(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs,
+                               const float* relu_mask, float* gx, int shifts, int c, int h, int w, int accumulate, maua_stream_t stream);
+int maua_flip_gram_mse_ledger_supported(int mirrors, int c);
+int maua_flip_gram_fwd_mse_ledger(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c,
+                                  int h, int w, const float* target, const double* loss_scales, const double* grad_scales, float* dmat,
+                                  double* ledger, int slot, void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_flip_gram_bwd_masked(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, const float* relu_mask,
+                              float* gx, int mirrors, int c, int h, int w, int accumulate, maua_stream_t stream);
+
 /* ---- total variation: loss.TVLoss.forward, loss.py:224-233, and its autograd ---------------------- */
 /* loss_out[0] = strength * (sum|dy| + sum|dx|); grad (+)= strength * d/dx.  workspace as for the MSE. */
 int maua_tv_fwd_bwd(const float* x, float* grad, int n, int c, int h, int w, float strength, int accumulate,

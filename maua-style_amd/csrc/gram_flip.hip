@@ -16,6 +16,8 @@
 // sigma(p) - 3 .. sigma(p), one 16-byte load reversed in registers; UD reads whole rows ascending.  A quad that crosses a row end or the plane's
 // end goes element by element.  sigma(p) lies inside F exactly when p does: the mask of a quad (p < H W) is computed from indices first and
 // decides which addresses are formed at all.
+// For the fused engine: a finishing kernel that also forms D_m = grad_scale_m (G_m - T_m) and the mirrors' loss as one ledger record
+// (gf_finish_mse_kernel), and a ReLU mask in the backward kernel's epilogue (gf_bwd_kernel's MASK flag).
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
@@ -206,14 +208,103 @@ gf_finish_kernel(const float* __restrict__ partial, float* __restrict__ gram, Gf
     gm[(int64_t)gj * C + gi] = g;
 }
 
+// gf_finish_kernel and the MSE against the mirrors' targets in one launch: grid (tile pairs, 16 / FQ, M), every thread owns FQ elements of
+// the 64x64 tile (e = 256 (FQ blockIdx.y + u) + tid); in a diagonal tile the elements with er <= ec only are live.  Each live element's slab
+// values are added in index order in fp64 exactly as gf_finish_kernel adds them (the same bits; the other threads fold an element they do
+// not use, which keeps every load unconditional); the target elements - read on and above
+// the diagonal only - are requested first, so they arrive beside the slabs and not behind them, and the loads of the thread's FQ elements
+// for sixteen slabs are requested together.  D_m = grad_scale_m (G_m - T_m) is formed once per live element and written with its mirror
+// like G_m (bit-symmetric whatever the target holds below its diagonal); exact zeros for a mirror with grad_scale_m == 0.  The workgroup's
+// share of loss_scale_m sum (G_m - T_m)^2 - an element off the diagonal counts twice - is one partial sum of the call's ledger record
+// (scale 1): M x pairs x 16 / FQ partial sums, a fixed order, no atomics.  The host takes the smallest FQ of 1, 2, 4 whose partial sums fit
+// the record (gf_finish_split): three mirrors of 512 channels take FQ = 1 (1728 sums).
+struct GfTerms {  // launch argument: the host coefficient arrays of one maua_flip_gram_fwd_mse_ledger call
+    double loss[GF_MMAX], grad[GF_MMAX];
+};
+constexpr int GF_FQ_MAX = 4;  // most elements per thread: 16 / 4 workgroups per (mirror, tile pair)
+template <int FQ>
+__global__ void __launch_bounds__(256)
+gf_finish_mse_kernel(const float* __restrict__ partial, float* __restrict__ gram, GfMirrors mr, GfTerms tw, int C, int npairs, int ksplit,
+                     const float* __restrict__ target, float* __restrict__ dmat, double* __restrict__ rec) {
+    __shared__ double scratch[16];
+    const int s = blockIdx.z;
+    const int ntile = (C + GF_T - 1) / GF_T;
+    int ti, tj;
+    gf_pair(blockIdx.x, ntile, &ti, &tj);
+    const double ls = tw.loss[s];
+    const float gs = (float)tw.grad[s];
+    const int64_t mat = (int64_t)s * C * C;
+    int e[FQ], gi[FQ], gj[FQ];
+    bool live[FQ];
+    float tg[FQ];
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) {
+        e[u] = (blockIdx.y * FQ + u) * 256 + threadIdx.x;
+        const int er = e[u] / GF_T, ec = e[u] % GF_T;
+        gi[u] = ti * GF_T + er;
+        gj[u] = tj * GF_T + ec;
+        live[u] = gi[u] < C && gj[u] < C && !(ti == tj && er > ec);
+        tg[u] = live[u] ? target[mat + (int64_t)gi[u] * C + gj[u]] : 0.f;
+        // every thread folds some element of the slabs, so that the loads below carry no condition and stay in flight together: an element
+        // below the diagonal of a diagonal tile folds its row's diagonal element (the cache lines its wave reads anyway; the sum is not used)
+        if (ti == tj && er > ec) e[u] = er * GF_T + er;
+    }
+    const float* base = partial + ((int64_t)s * npairs + blockIdx.x) * ksplit * (GF_T * GF_T);
+    double sd[FQ];
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) sd[u] = 0.0;
+    int k = 0;
+    for (; k + 15 < ksplit; k += 16) {  // 16 FQ loads in flight, each element's additions in the order of a plain loop
+        float v[FQ][16];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u)
+#pragma unroll
+            for (int w = 0; w < 16; ++w) v[u][w] = base[(int64_t)(k + w) * (GF_T * GF_T) + e[u]];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u)
+#pragma unroll
+            for (int w = 0; w < 16; ++w) sd[u] += (double)v[u][w];
+    }
+    for (; k < ksplit; ++k) {
+        float v[FQ];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u) v[u] = base[(int64_t)k * (GF_T * GF_T) + e[u]];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u) sd[u] += (double)v[u];
+    }
+    double sq = 0.0;
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) {
+        if (!live[u]) continue;
+        const float g = (float)(sd[u] * mr.factor[s]);
+        const float d = g - tg[u];
+        const float dv = gs != 0.f ? gs * d : 0.f;
+        const int64_t up = mat + (int64_t)gi[u] * C + gj[u], low = mat + (int64_t)gj[u] * C + gi[u];
+        gram[up] = g;
+        gram[low] = g;
+        dmat[up] = dv;
+        dmat[low] = dv;
+        if (ls != 0.0) sq += (gi[u] != gj[u] ? 2.0 : 1.0) * ((double)d * (double)d);
+    }
+    sq = block_sum(sq, scratch);
+    if (threadIdx.x == 0) {
+        rec[2 + ((int64_t)s * npairs + blockIdx.x) * gridDim.y + blockIdx.y] = ls != 0.0 ? sq * ls : 0.0;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && s == 0) {
+            rec[0] = (double)(gridDim.x * gridDim.y * gridDim.z);
+            rec[1] = 1.0;
+        }
+    }
+}
+
 // Backward.  Workgroup = 64 output channels x 256 pixels, wave = 64 x 64 (2 x 2 accumulators), 32 input channels per LDS stage,
 // double-buffered (80 KB); the stages run over (mirror, channel block).  A mirror whose coef is 0 is left out.
 constexpr int GFB_KC = 32, GFB_PX = 256, GFB_CO = 64;
 
-template <bool ACC>
+// MASK: the sums (and what they were accumulated into) are written as 0 where relu_mask[c][p] <= 0 (gram_bwd_kernel's pre-masked gradients).
+template <bool ACC, bool MASK>
 __global__ void __launch_bounds__(256)
-gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ gx, GfMirrors mr, int M,
-              int C, int H, int W) {
+gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, const float* __restrict__ relu_mask,
+              float* __restrict__ gx, GfMirrors mr, int M, int C, int H, int W) {
     extern __shared__ __attribute__((aligned(16))) float smem_f32[];  // 2 x (Xl[32][256] + Wl[32][64])
     float* smem = smem_f32;
     constexpr int BUF = GFB_KC * GFB_PX + GFB_KC * GFB_CO;
@@ -335,18 +426,23 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             // read-modify-write in two sweeps: all loads of the 16 registers first, then all stores (gram_bwd_kernel)
-            float prev[16];
+            float prev[16], mk[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
                 const bool ok = pix < HW && co < C;
+                const int64_t o = ok ? (int64_t)co * HW + pix : 0;
                 prev[q] = 0.f;
-                if constexpr (ACC) prev[q] = gx[ok ? (int64_t)co * HW + pix : 0];
+                mk[q] = 1.f;
+                if constexpr (ACC) prev[q] = gx[o];
+                if constexpr (MASK) mk[q] = relu_mask[o];
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
-                if (pix < HW && co < C) gx[(int64_t)co * HW + pix] = acc[t][u][q] + prev[q];
+                float v = acc[t][u][q] + prev[q];
+                if constexpr (MASK) v = mk[q] <= 0.f ? 0.f : v;
+                if (pix < HW && co < C) gx[(int64_t)co * HW + pix] = v;
             }
         }
     }
@@ -365,6 +461,14 @@ static void gf_plan(int c, int64_t hw, int* npairs, int* ksplit, int* chunk) {
     const int64_t ch = ((hw + want - 1) / want + GF_K - 1) / GF_K * GF_K;
     *chunk = (int)ch;
     *ksplit = (int)((hw + ch - 1) / ch);
+}
+
+// elements per thread of gf_finish_mse_kernel: the smallest of 1, 2, 4 for which mirrors x pairs x 16 / FQ partial sums fit one ledger
+// record (0: not even GF_FQ_MAX does)
+static int gf_finish_split(int mirrors, int64_t npairs) {
+    for (int fq = 1; fq <= GF_FQ_MAX; fq *= 2)
+        if ((int64_t)mirrors * npairs * (GF_T * GF_T / 256 / fq) <= LEDGER_MAX) return fq;
+    return 0;
 }
 
 static bool gf_shape_ok(int mirrors, int c, int h, int w) {
@@ -401,16 +505,25 @@ size_t maua_gram_flip_workspace_bytes(int mirrors, int c, int h, int w) {
     return (size_t)mirrors * npairs * ksplit * GF_T * GF_T * sizeof(float);
 }
 
-int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c, int h, int w,
-                       void* workspace, size_t workspace_bytes, maua_stream_t stream) {
-    MAUA_REQUIRE(f && kinds && scales && gram && workspace, MAUA_E_INVAL, "gram_flip_fwd: null pointer");
-    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "gram_flip_fwd: %d mirrors (1 .. %d), %d channels, %d x %d pixels", mirrors,
-                 GF_MMAX, c, h, w);
+// maua_gram_flip_fwd; with `mse` the finishing launch is gf_finish_mse_kernel
+struct FlipMse {
+    const float* target;
+    const double *loss_scales, *grad_scales;
+    float* dmat;
+    double* rec;
+};
+static int gf_forward(const char* who, const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c,
+                      int h, int w, void* workspace, size_t workspace_bytes, const FlipMse* mse, maua_stream_t stream) {
+    MAUA_REQUIRE(f && kinds && scales && gram && workspace, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "%s: %d mirrors (1 .. %d), %d channels, %d x %d pixels", who, mirrors, GF_MMAX,
+                 c, h, w);
     GfMirrors mr;
-    int rc = gf_pack("gram_flip_fwd", kinds, scales, mirrors, &mr);
+    int rc = gf_pack(who, kinds, scales, mirrors, &mr);
     if (rc) return rc;
+    MAUA_REQUIRE(!mse || maua_flip_gram_mse_ledger_supported(mirrors, c), MAUA_E_UNSUPPORTED,
+                 "%s: %d mirrors of %d channels need more than %d partial sums", who, mirrors, c, LEDGER_MAX);
     const size_t need = maua_gram_flip_workspace_bytes(mirrors, c, h, w);
-    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "gram_flip_fwd: workspace %zu < %zu", workspace_bytes, need);
+    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
     int npairs, ksplit, chunk;
     gf_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
     hipStream_t s = (hipStream_t)stream;
@@ -418,29 +531,80 @@ int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, cons
                        chunk);
     rc = check_launch("gf_partial_kernel");
     if (rc) return rc;
+    if (mse) {
+        GfTerms tw;
+        for (int i = 0; i < GF_MMAX; ++i) {
+            tw.loss[i] = i < mirrors ? mse->loss_scales[i] : 0.0;
+            tw.grad[i] = i < mirrors ? mse->grad_scales[i] : 0.0;
+        }
+        const int fq = gf_finish_split(mirrors, npairs);
+        auto finish = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(npairs, GF_T * GF_T / 256 / fq, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, tw, c,
+                               npairs, ksplit, mse->target, mse->dmat, mse->rec);
+        };
+        if (fq == 1) finish(gf_finish_mse_kernel<1>);
+        else if (fq == 2) finish(gf_finish_mse_kernel<2>);
+        else finish(gf_finish_mse_kernel<4>);
+        return check_launch("gf_finish_mse_kernel");
+    }
     hipLaunchKernelGGL(gf_finish_kernel, dim3(npairs, GF_T * GF_T / 256, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, c, npairs,
                        ksplit);
     return check_launch("gf_finish_kernel");
 }
 
-int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
-                       int h, int w, int accumulate, maua_stream_t stream) {
-    MAUA_REQUIRE(d && f && kinds && coefs && gx, MAUA_E_INVAL, "gram_flip_bwd: null pointer");
-    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "gram_flip_bwd: %d mirrors (1 .. %d), %d channels, %d x %d pixels", mirrors,
-                 GF_MMAX, c, h, w);
+static int gf_backward(const char* who, const float* d, const float* f, const float* mean, const int* kinds, const double* coefs,
+                       const float* relu_mask, float* gx, int mirrors, int c, int h, int w, int accumulate, maua_stream_t stream) {
+    MAUA_REQUIRE(d && f && kinds && coefs && gx, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(gf_shape_ok(mirrors, c, h, w), MAUA_E_UNSUPPORTED, "%s: %d mirrors (1 .. %d), %d channels, %d x %d pixels", who, mirrors, GF_MMAX,
+                 c, h, w);
     GfMirrors mr;
-    const int rc = gf_pack("gram_flip_bwd", kinds, coefs, mirrors, &mr);
+    const int rc = gf_pack(who, kinds, coefs, mirrors, &mr);
     if (rc) return rc;
     const int64_t hw = (int64_t)h * w;
     constexpr size_t lds = 2ull * (GFB_KC * GFB_PX + GFB_KC * GFB_CO) * sizeof(float);
     const dim3 grid((unsigned)((hw + GFB_PX - 1) / GFB_PX), (unsigned)((c + GFB_CO - 1) / GFB_CO));
     auto launch = [&](auto kernel) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, gx, mr, mirrors, c, h, w);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, relu_mask, gx, mr, mirrors, c, h, w);
     };
-    if (accumulate) launch(gf_bwd_kernel<true>);
-    else launch(gf_bwd_kernel<false>);
+    if (relu_mask) {
+        if (accumulate) launch(gf_bwd_kernel<true, true>);
+        else launch(gf_bwd_kernel<false, true>);
+    } else {
+        if (accumulate) launch(gf_bwd_kernel<true, false>);
+        else launch(gf_bwd_kernel<false, false>);
+    }
     return check_launch("gf_bwd_kernel");
+}
+
+int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c, int h, int w,
+                       void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    return gf_forward("gram_flip_fwd", f, mean, kinds, scales, gram, mirrors, c, h, w, workspace, workspace_bytes, nullptr, stream);
+}
+
+int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
+                       int h, int w, int accumulate, maua_stream_t stream) {
+    return gf_backward("gram_flip_bwd", d, f, mean, kinds, coefs, nullptr, gx, mirrors, c, h, w, accumulate, stream);
+}
+
+int maua_flip_gram_mse_ledger_supported(int mirrors, int c) {
+    if (!gf_shape_ok(mirrors, c, 1, 1)) return 0;
+    const int64_t nt = (c + GF_T - 1) / GF_T;
+    return gf_finish_split(mirrors, nt * (nt + 1) / 2) != 0 ? 1 : 0;
+}
+
+int maua_flip_gram_fwd_mse_ledger(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c,
+                                  int h, int w, const float* target, const double* loss_scales, const double* grad_scales, float* dmat,
+                                  double* ledger, int slot, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    MAUA_REQUIRE(target && loss_scales && grad_scales && dmat && ledger && slot >= 0 && slot < (1 << 28), MAUA_E_INVAL,
+                 "flip_gram_fwd_mse_ledger: bad args");
+    const FlipMse m{target, loss_scales, grad_scales, dmat, ledger + (int64_t)slot * LEDGER_STRIDE};
+    return gf_forward("flip_gram_fwd_mse_ledger", f, mean, kinds, scales, gram, mirrors, c, h, w, workspace, workspace_bytes, &m, stream);
+}
+
+int maua_flip_gram_bwd_masked(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, const float* relu_mask,
+                              float* gx, int mirrors, int c, int h, int w, int accumulate, maua_stream_t stream) {
+    return gf_backward("flip_gram_bwd_masked", d, f, mean, kinds, coefs, relu_mask, gx, mirrors, c, h, w, accumulate, stream);
 }
 
 }  // extern "C"

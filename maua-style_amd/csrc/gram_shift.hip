@@ -14,6 +14,8 @@
 // shift gives two runs of stages of one accumulation, D_s^T against X read at q - off_s and D_s against X read at q + off_s.  D_s^T is D_s
 // written to LDS transposed, never to memory.
 // No load leaves F: the validity mask of a pixel quad is computed from indices first and decides which addresses are formed at all.
+// For the fused engine: a finishing kernel that also forms D_s = grad_scale_s (G_s - T_s) and the shifts' loss as one ledger record
+// (gs_finish_mse_kernel), and a ReLU mask in the backward kernel's epilogue (gs_bwd_kernel's MASK flag).
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
 #include <stdlib.h>
 
@@ -181,15 +183,91 @@ gs_finish_kernel(const float* __restrict__ partial, float* __restrict__ gram, Gs
     if (gi < C && gj < C) gram[((int64_t)s * C + gi) * C + gj] = (float)(sd * sh.factor[s]);
 }
 
+// gs_finish_kernel and the MSE against the shifts' targets in one launch: grid (tile pairs, 16 / FQ, S), every thread owns FQ elements of the
+// 64x64 tile (e = 256 (FQ blockIdx.y + u) + tid).  Each element's slab values are added in index order in fp64 exactly as gs_finish_kernel
+// adds them (the same bits); the target elements are requested first, so they arrive beside the slabs and not behind them, and the loads
+// of the thread's FQ elements for eight slabs are requested together.  D_s = grad_scale_s (G_s - T_s) element by element (G_s is not
+// symmetric); exact zeros for a shift with grad_scale_s == 0.  The workgroup's share of loss_scale_s sum (G_s - T_s)^2 is one partial sum of
+// the call's ledger record (scale 1): S x pairs x 16 / FQ partial sums, a fixed order, no atomics.  The host takes the smallest FQ of 1, 2,
+// 4 whose partial sums fit the record (gs_finish_split): four shifts of 512 channels take FQ = 1 (4096 sums), sixteen FQ = 4.
+struct GsTerms {  // launch argument: the host coefficient arrays of one maua_shift_gram_fwd_mse_ledger call
+    double loss[GS_SMAX], grad[GS_SMAX];
+};
+constexpr int GS_FQ_MAX = 4;  // most elements per thread: 16 / 4 workgroups per (shift, tile pair)
+template <int FQ>
+__global__ void __launch_bounds__(256)
+gs_finish_mse_kernel(const float* __restrict__ partial, float* __restrict__ gram, GsShifts sh, GsTerms tw, int C, int npairs, int ksplit,
+                     const float* __restrict__ target, float* __restrict__ dmat, double* __restrict__ rec) {
+    __shared__ double scratch[16];
+    const int s = blockIdx.z;
+    const int ntile = (C + GS_T - 1) / GS_T;
+    const int ti = blockIdx.x / ntile, tj = blockIdx.x % ntile;
+    const double ls = tw.loss[s];
+    const float gs = (float)tw.grad[s];
+    const int64_t mat = (int64_t)s * C * C;
+    int e[FQ];
+    int64_t at[FQ];  // the element's place in its matrix, -1 outside it
+    float tg[FQ];
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) {
+        e[u] = (blockIdx.y * FQ + u) * 256 + threadIdx.x;
+        const int gi = ti * GS_T + e[u] / GS_T, gj = tj * GS_T + e[u] % GS_T;
+        at[u] = (gi < C && gj < C) ? mat + (int64_t)gi * C + gj : -1;
+        tg[u] = at[u] >= 0 ? target[at[u]] : 0.f;
+    }
+    const float* base = partial + ((int64_t)s * npairs + blockIdx.x) * ksplit * (GS_T * GS_T);
+    double sd[FQ];
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) sd[u] = 0.0;
+    int k = 0;
+    for (; k + 7 < ksplit; k += 8) {  // 8 FQ loads in flight, each element's additions in the order of a plain loop
+        float v[FQ][8];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u)
+#pragma unroll
+            for (int w = 0; w < 8; ++w) v[u][w] = base[(int64_t)(k + w) * (GS_T * GS_T) + e[u]];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u)
+#pragma unroll
+            for (int w = 0; w < 8; ++w) sd[u] += (double)v[u][w];
+    }
+    for (; k < ksplit; ++k) {
+        float v[FQ];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u) v[u] = base[(int64_t)k * (GS_T * GS_T) + e[u]];
+#pragma unroll
+        for (int u = 0; u < FQ; ++u) sd[u] += (double)v[u];
+    }
+    double sq = 0.0;
+#pragma unroll
+    for (int u = 0; u < FQ; ++u) {
+        if (at[u] < 0) continue;
+        const float g = (float)(sd[u] * sh.factor[s]);
+        const float d = g - tg[u];
+        gram[at[u]] = g;
+        dmat[at[u]] = gs != 0.f ? gs * d : 0.f;
+        if (ls != 0.0) sq += (double)d * (double)d;
+    }
+    sq = block_sum(sq, scratch);
+    if (threadIdx.x == 0) {
+        rec[2 + ((int64_t)s * npairs + blockIdx.x) * gridDim.y + blockIdx.y] = ls != 0.0 ? sq * ls : 0.0;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && s == 0) {
+            rec[0] = (double)(gridDim.x * gridDim.y * gridDim.z);
+            rec[1] = 1.0;
+        }
+    }
+}
+
 // Backward.  Workgroup = 64 output channels x 256 pixels, wave = 64 x 64 (2 x 2 accumulators), 32 input channels per LDS stage,
 // double-buffered (80 KB); the stages run over (shift, term, channel block): term 0 is D_s^T against X at q - off_s, term 1 D_s against X
 // at q + off_s.  A (shift, term) whose mask is empty over the workgroup's 256 pixels is left out.
 constexpr int GSB_KC = 32, GSB_PX = 256, GSB_CO = 64;
 
-template <bool ACC>
+// MASK: the sums (and what they were accumulated into) are written as 0 where relu_mask[c][p] <= 0 (gram_bwd_kernel's pre-masked gradients).
+template <bool ACC, bool MASK>
 __global__ void __launch_bounds__(256)
-gs_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ gx, GsShifts sh, int S,
-              int C, int H, int W) {
+gs_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, const float* __restrict__ relu_mask,
+              float* __restrict__ gx, GsShifts sh, int S, int C, int H, int W) {
     extern __shared__ __attribute__((aligned(16))) float smem_f32[];  // 2 x (Xl[32][256] + Wl[32][64])
     float* smem = smem_f32;
     constexpr int BUF = GSB_KC * GSB_PX + GSB_KC * GSB_CO;
@@ -325,18 +403,23 @@ gs_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             // read-modify-write in two sweeps: all loads of the 16 registers first, then all stores (gram_bwd_kernel)
-            float prev[16];
+            float prev[16], mk[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
                 const bool ok = pix < HW && co < C;
+                const int64_t o = ok ? (int64_t)co * HW + pix : 0;
                 prev[q] = 0.f;
-                if constexpr (ACC) prev[q] = gx[ok ? (int64_t)co * HW + pix : 0];
+                mk[q] = 1.f;
+                if constexpr (ACC) prev[q] = gx[o];
+                if constexpr (MASK) mk[q] = relu_mask[o];
             }
 #pragma unroll
             for (int q = 0; q < 16; ++q) {
                 const int co = co0 + t * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
-                if (pix < HW && co < C) gx[(int64_t)co * HW + pix] = acc[t][u][q] + prev[q];
+                float v = acc[t][u][q] + prev[q];
+                if constexpr (MASK) v = mk[q] <= 0.f ? 0.f : v;
+                if (pix < HW && co < C) gx[(int64_t)co * HW + pix] = v;
             }
         }
     }
@@ -355,6 +438,14 @@ static void gs_plan(int c, int64_t hw, int* npairs, int* ksplit, int64_t* chunk)
     const int64_t ch = ((hw + want - 1) / want + GS_K - 1) / GS_K * GS_K;
     *chunk = ch;
     *ksplit = (int)((hw + ch - 1) / ch);
+}
+
+// elements per thread of gs_finish_mse_kernel: the smallest of 1, 2, 4 for which shifts x pairs x 16 / FQ partial sums fit one ledger record
+// (0: not even GS_FQ_MAX does)
+static int gs_finish_split(int shifts, int64_t npairs) {
+    for (int fq = 1; fq <= GS_FQ_MAX; fq *= 2)
+        if ((int64_t)shifts * npairs * (GS_T * GS_T / 256 / fq) <= LEDGER_MAX) return fq;
+    return 0;
 }
 
 static bool gs_shape_ok(int shifts, int c, int h, int w) {
@@ -396,16 +487,25 @@ size_t maua_gram_shift_workspace_bytes(int shifts, int c, int h, int w) {
     return (size_t)shifts * npairs * ksplit * GS_T * GS_T * sizeof(float);
 }
 
-int maua_gram_shift_fwd(const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram, int shifts,
-                        int c, int h, int w, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
-    MAUA_REQUIRE(f && axes && deltas && scales && gram && workspace, MAUA_E_INVAL, "gram_shift_fwd: null pointer");
-    MAUA_REQUIRE(gs_shape_ok(shifts, c, h, w), MAUA_E_UNSUPPORTED, "gram_shift_fwd: %d shifts (1 .. %d), %d channels, %d x %d pixels", shifts,
-                 GS_SMAX, c, h, w);
+// maua_gram_shift_fwd; with `mse` the finishing launch is gs_finish_mse_kernel
+struct ShiftMse {
+    const float* target;
+    const double *loss_scales, *grad_scales;
+    float* dmat;
+    double* rec;
+};
+static int gs_forward(const char* who, const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram,
+                      int shifts, int c, int h, int w, void* workspace, size_t workspace_bytes, const ShiftMse* mse, maua_stream_t stream) {
+    MAUA_REQUIRE(f && axes && deltas && scales && gram && workspace, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(gs_shape_ok(shifts, c, h, w), MAUA_E_UNSUPPORTED, "%s: %d shifts (1 .. %d), %d channels, %d x %d pixels", who, shifts, GS_SMAX, c,
+                 h, w);
     GsShifts sh;
-    int rc = gs_pack("gram_shift_fwd", axes, deltas, scales, shifts, h, w, &sh);
+    int rc = gs_pack(who, axes, deltas, scales, shifts, h, w, &sh);
     if (rc) return rc;
+    MAUA_REQUIRE(!mse || maua_shift_gram_mse_ledger_supported(shifts, c), MAUA_E_UNSUPPORTED,
+                 "%s: %d shifts of %d channels need more than %d partial sums", who, shifts, c, LEDGER_MAX);
     const size_t need = maua_gram_shift_workspace_bytes(shifts, c, h, w);
-    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "gram_shift_fwd: workspace %zu < %zu", workspace_bytes, need);
+    MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
     int npairs, ksplit;
     int64_t chunk;
     gs_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
@@ -414,29 +514,80 @@ int maua_gram_shift_fwd(const float* f, const float* mean, const int* axes, cons
                        chunk);
     rc = check_launch("gs_partial_kernel");
     if (rc) return rc;
+    if (mse) {
+        GsTerms tw;
+        for (int i = 0; i < GS_SMAX; ++i) {
+            tw.loss[i] = i < shifts ? mse->loss_scales[i] : 0.0;
+            tw.grad[i] = i < shifts ? mse->grad_scales[i] : 0.0;
+        }
+        const int fq = gs_finish_split(shifts, npairs);
+        auto finish = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(npairs, GS_T * GS_T / 256 / fq, shifts), dim3(256), 0, s, (const float*)workspace, gram, sh, tw, c, npairs,
+                               ksplit, mse->target, mse->dmat, mse->rec);
+        };
+        if (fq == 1) finish(gs_finish_mse_kernel<1>);
+        else if (fq == 2) finish(gs_finish_mse_kernel<2>);
+        else finish(gs_finish_mse_kernel<4>);
+        return check_launch("gs_finish_mse_kernel");
+    }
     hipLaunchKernelGGL(gs_finish_kernel, dim3(npairs, GS_T * GS_T / 256, shifts), dim3(256), 0, s, (const float*)workspace, gram, sh, c, npairs,
                        ksplit);
     return check_launch("gs_finish_kernel");
 }
 
-int maua_gram_shift_bwd(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs, float* gx,
-                        int shifts, int c, int h, int w, int accumulate, maua_stream_t stream) {
-    MAUA_REQUIRE(d && f && axes && deltas && coefs && gx, MAUA_E_INVAL, "gram_shift_bwd: null pointer");
-    MAUA_REQUIRE(gs_shape_ok(shifts, c, h, w), MAUA_E_UNSUPPORTED, "gram_shift_bwd: %d shifts (1 .. %d), %d channels, %d x %d pixels", shifts,
-                 GS_SMAX, c, h, w);
+static int gs_backward(const char* who, const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs,
+                       const float* relu_mask, float* gx, int shifts, int c, int h, int w, int accumulate, maua_stream_t stream) {
+    MAUA_REQUIRE(d && f && axes && deltas && coefs && gx, MAUA_E_INVAL, "%s: null pointer", who);
+    MAUA_REQUIRE(gs_shape_ok(shifts, c, h, w), MAUA_E_UNSUPPORTED, "%s: %d shifts (1 .. %d), %d channels, %d x %d pixels", who, shifts, GS_SMAX, c,
+                 h, w);
     GsShifts sh;
-    const int rc = gs_pack("gram_shift_bwd", axes, deltas, coefs, shifts, h, w, &sh);
+    const int rc = gs_pack(who, axes, deltas, coefs, shifts, h, w, &sh);
     if (rc) return rc;
     const int64_t hw = (int64_t)h * w;
     constexpr size_t lds = 2ull * (GSB_KC * GSB_PX + GSB_KC * GSB_CO) * sizeof(float);
     const dim3 grid((unsigned)((hw + GSB_PX - 1) / GSB_PX), (unsigned)((c + GSB_CO - 1) / GSB_CO));
     auto launch = [&](auto kernel) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, gx, sh, shifts, c, h, w);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, relu_mask, gx, sh, shifts, c, h, w);
     };
-    if (accumulate) launch(gs_bwd_kernel<true>);
-    else launch(gs_bwd_kernel<false>);
+    if (relu_mask) {
+        if (accumulate) launch(gs_bwd_kernel<true, true>);
+        else launch(gs_bwd_kernel<false, true>);
+    } else {
+        if (accumulate) launch(gs_bwd_kernel<true, false>);
+        else launch(gs_bwd_kernel<false, false>);
+    }
     return check_launch("gs_bwd_kernel");
+}
+
+int maua_gram_shift_fwd(const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram, int shifts,
+                        int c, int h, int w, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    return gs_forward("gram_shift_fwd", f, mean, axes, deltas, scales, gram, shifts, c, h, w, workspace, workspace_bytes, nullptr, stream);
+}
+
+int maua_gram_shift_bwd(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs, float* gx,
+                        int shifts, int c, int h, int w, int accumulate, maua_stream_t stream) {
+    return gs_backward("gram_shift_bwd", d, f, mean, axes, deltas, coefs, nullptr, gx, shifts, c, h, w, accumulate, stream);
+}
+
+int maua_shift_gram_mse_ledger_supported(int shifts, int c) {
+    if (!gs_shape_ok(shifts, c, 1, 1)) return 0;
+    const int64_t nt = (c + GS_T - 1) / GS_T;
+    return gs_finish_split(shifts, nt * nt) != 0 ? 1 : 0;
+}
+
+int maua_shift_gram_fwd_mse_ledger(const float* f, const float* mean, const int* axes, const int* deltas, const double* scales, float* gram,
+                                   int shifts, int c, int h, int w, const float* target, const double* loss_scales, const double* grad_scales,
+                                   float* dmat, double* ledger, int slot, void* workspace, size_t workspace_bytes, maua_stream_t stream) {
+    MAUA_REQUIRE(target && loss_scales && grad_scales && dmat && ledger && slot >= 0 && slot < (1 << 28), MAUA_E_INVAL,
+                 "shift_gram_fwd_mse_ledger: bad args");
+    const ShiftMse m{target, loss_scales, grad_scales, dmat, ledger + (int64_t)slot * LEDGER_STRIDE};
+    return gs_forward("shift_gram_fwd_mse_ledger", f, mean, axes, deltas, scales, gram, shifts, c, h, w, workspace, workspace_bytes, &m, stream);
+}
+
+int maua_shift_gram_bwd_masked(const float* d, const float* f, const float* mean, const int* axes, const int* deltas, const double* coefs,
+                               const float* relu_mask, float* gx, int shifts, int c, int h, int w, int accumulate, maua_stream_t stream) {
+    return gs_backward("shift_gram_bwd_masked", d, f, mean, axes, deltas, coefs, relu_mask, gx, shifts, c, h, w, accumulate, stream);
 }
 
 }  // extern "C"

@@ -57,6 +57,20 @@ def guided_coefficients(strength, video_style_factor, normalize, channels, activ
     return [lw / cc if o else 0.0 for o in on], [gw * 4.0 / cc if o else 0.0 for o in on]
 
 
+def term_coefficients(strength, normalize, channels, factors):
+    """(loss_scales, grad_scales) of the shift / mirror terms of a StyleLoss for hip.gram_shift_fwd_mse_ledger / hip.gram_flip_fwd_mse_ledger,
+    one entry per factor (each shift entry: shift_factor; LR / UD: flip_factor; the point mirror: rotation_factor) - what
+    loss.StyleLoss.static_loss does for one frame: the terms sit inside the static scalar t = mse(G, T) + sum_k factor_k mse(G_k, T_k), which
+    enters the loss as strength * t and the gradient with gw = strength, or through ScaleGradients (sign * strength^2) with `normalize`;
+    the dynamic term (video_style_factor) carries none of them.  loss_scale_k = strength * factor_k / C^2; grad_scale_k = gw * factor_k *
+    2 / C^2 scales G_k - T_k into dL/dG_k, the matrix both backward kernels take as given (they add the transpose themselves; their
+    1 / (C n_k) is the backward `coefs` = the forward `scales`).  Pure host arithmetic."""
+    s = strength
+    gw = _scale_grad_coeff(s, s) if normalize else s
+    cc = float(channels) * float(channels)
+    return [s * float(k) / cc for k in factors], [gw * float(k) * 2.0 / cc for k in factors]
+
+
 class _Step:
     __slots__ = ("kind", "mod", "relu", "src", "dst", "slot", "k", "stride", "pad", "ceil", "mode")
 
@@ -102,9 +116,10 @@ class StyleEngine:
             elif isinstance(m, loss_mod.StyleLoss):
                 if getattr(m, "guide", None) is not None and not plan.on("guided_engine"):
                     raise UnsupportedNet("guided StyleLoss runs on the module path")
-                if m.shift_factor > 0:
+                # (with the module's `terms_engine` on, _prepare plans the step as a terms step instead)
+                if m.shift_factor > 0 and not getattr(m, "terms_engine", False):
                     raise UnsupportedNet("shifted StyleLoss runs on the module path")
-                if m.mirror_kinds():
+                if m.mirror_kinds() and not getattr(m, "terms_engine", False):
                     raise UnsupportedNet("mirrored StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
@@ -153,8 +168,16 @@ class StyleEngine:
         regions = {id(s): s.mod.guide.shape[0] for s in self.steps if s.kind == "style" and getattr(s.mod, "guide", None) is not None} \
             if plan.on("guided_engine") else {}
         made_for = (self.independent, self.batch_hint) + ((tuple(regions.get(id(s)) for s in self.steps if s.kind == "style"),) if regions else ())
+        # StyleLoss.terms_engine: a style step whose module has shift or mirror terms is planned as a terms step (its plain Gram matrix
+        # through its own fused launch, the terms' matrices, D and loss through csrc/gram_shift.hip / gram_flip.hip, none of the whole-plane
+        # fusions below); which modules ask for which terms is part of what the plan was made for
+        tsig = tuple((s.mod.shift_factor > 0, tuple(s.mod.mirror_kinds())) if getattr(s.mod, "terms_engine", False) else None
+                     for s in self.steps if s.kind == "style")
+        if any(t is not None and (t[0] or t[1]) for t in tsig):
+            made_for += (("terms",) + tsig,)
         if self.shape == tuple(x.shape) and getattr(self, "prepared_for", None) == made_for:
             self._refresh_guided()
+            self._refresh_terms()
             return
         dev = x.device
         B = x.shape[0]
@@ -179,6 +202,31 @@ class StyleEngine:
             if id(s) in regions and not hip.gram_guided_mse_ledger_supported(regions[id(s)], shapes[s.src][1]):
                 self.shape = None  # (no plan was made)
                 raise UnsupportedNet(f"guided StyleLoss: {regions[id(s)]} regions of {shapes[s.src][1]} channels do not fit one ledger record")
+        terms = {}  # id(step) -> (has shift terms at this size, mirror kinds)
+        for s in self.steps:
+            if s.kind == "style" and getattr(s.mod, "terms_engine", False):
+                c, h, w = shapes[s.src][1:]
+                shift = s.mod.shift_factor > 0 and bool(loss_mod.shift_deltas(h, w))  # (maps under 32 pixels have no shift)
+                kinds = tuple(s.mod.mirror_kinds())
+                if not (shift or kinds):
+                    continue
+                why = None
+                if B != 1 or self.independent:
+                    why = "one frame per evaluation (B = 1, no independent frames)"
+                elif not plan.on("loss_ledger"):
+                    why = "needs the loss ledger (planner field loss_ledger)"
+                elif shift and s.mod.use_covariance:
+                    why = "shift_factor > 0 with use_covariance (the term through the row means) runs on the module path"
+                elif shift and not (hip.gram_shift_supported(2 * len(loss_mod.shift_deltas(h, w)), c, h, w) and
+                                    hip.gram_shift_mse_ledger_supported(2 * len(loss_mod.shift_deltas(h, w)), c)):
+                    why = f"{2 * len(loss_mod.shift_deltas(h, w))} shifts of {c} channels do not fit one ledger record"
+                elif kinds and not (hip.gram_flip_supported(len(kinds), c, h, w) and hip.gram_flip_mse_ledger_supported(len(kinds), c)):
+                    why = f"{len(kinds)} mirrors of {c} channels do not fit one ledger record"
+                if why is not None:
+                    self.shape = None  # (no plan was made)
+                    raise UnsupportedNet(f"shifted / mirrored StyleLoss on the engine: {why}")
+                terms[id(s)] = (shift, kinds)
+        special = set(regions) | set(terms)  # style steps that take none of the whole-plane fusions
         self.act = {k: (None if k == 0 else torch.empty(v, device=dev)) for k, v in shapes.items()}
         self.gbuf = {k: torch.empty(v, device=dev) for k, v in shapes.items()}
         # 2x2/2 max pools on even planes keep their decisions (one byte per window) for the backward pass
@@ -192,6 +240,23 @@ class StyleEngine:
         # dynamic Gram term of a StyleLoss - each with its own slot behind the per-module ones
         self.terms = {}
         n_slots = max(len(self.losses), 1)
+        # terms steps: hidden slots behind the modules' own, one for the step's shift record and one for its mirror record (a ledger slot
+        # holds one record); _run adds them into the module's entry behind loss_ledger_sum
+        self.term_steps = {}
+        for s in self.steps:
+            if id(s) in terms:
+                shift, kinds = terms[id(s)]
+                c, h, w = shapes[s.src][1:]
+                td = dict(chw=(c, h, w), kinds=kinds, shift_slot=None, flip_slot=None, sig=None, shifts=[], coef=None, err=None,
+                          s_target=None, s_gram=None, s_dmat=None, f_target=None, f_gram=None, f_dmat=None)
+                if shift:
+                    td["shift_slot"], n_slots = n_slots, n_slots + 1
+                    ns = 2 * len(loss_mod.shift_deltas(h, w))  # (the most this size can use; the targets may share fewer)
+                    td["s_target"], td["s_gram"], td["s_dmat"] = (torch.zeros(ns, c, c, device=dev) for _ in range(3))
+                if kinds:
+                    td["flip_slot"], n_slots = n_slots, n_slots + 1
+                    td["f_target"], td["f_gram"], td["f_dmat"] = (torch.zeros(len(kinds), c, c, device=dev) for _ in range(3))
+                self.term_steps[id(s)] = td
         if B > 1 and not self.independent:
             for s in self.steps:
                 if s.kind in ("style", "content"):
@@ -264,7 +329,7 @@ class StyleEngine:
                     continue
                 on_src = [t for t in self.steps if t.kind in ("style", "content") and t.src == s.src]
                 c, h, w = shapes[s.src][1:]
-                if len(on_src) == 1 and on_src[0].kind == "style" and id(on_src[0]) not in regions and not on_src[0].mod.use_covariance and c % 16 == 0 and \
+                if len(on_src) == 1 and on_src[0].kind == "style" and id(on_src[0]) not in special and not on_src[0].mod.use_covariance and c % 16 == 0 and \
                         c <= max_c and self._x6_ok(s, s.mod.in_channels) and models_mod.conv3x3_bwd_is_x3w(s.mod, *shapes[s.dst][2:]):
                     bank = hip.conv_x3w_dmat_bank(c, dev, B)
                     if bank is not None:
@@ -282,7 +347,7 @@ class StyleEngine:
                         not self._x6_ok(s, 64):
                     continue
                 on_dst = [t for t in self.steps if t.kind == "style" and t.src == s.dst]
-                if len(on_dst) == 1 and id(on_dst[0]) not in regions and not on_dst[0].mod.use_covariance and hip.gram_mse_ledger_supported(64):
+                if len(on_dst) == 1 and id(on_dst[0]) not in special and not on_dst[0].mod.use_covariance and hip.gram_mse_ledger_supported(64):
                     h, w = shapes[s.src][2:]
                     slabs = hip.conv_image_gram_slabs(h, w, s.pad)
                     if 0 < slabs * 64 * 64 * 4 <= hip.gram_workspace_bytes(64, shapes[s.dst][2] * shapes[s.dst][3]):
@@ -311,6 +376,13 @@ class StyleEngine:
                 self.mean[id(s)] = (torch.empty(B, c, device=dev) if B > 1 else torch.empty(c, device=dev)) \
                     if s.mod.use_covariance else None
                 ws = max(ws, hip.gram_workspace_bytes(c, hw), 4 * c + 256)
+                td = self.term_steps.get(id(s))
+                if td is not None:
+                    h, w = shapes[s.src][2:]
+                    if td["s_target"] is not None:
+                        ws = max(ws, hip.gram_shift_workspace_bytes(td["s_target"].shape[0], c, h, w))
+                    if td["f_target"] is not None:
+                        ws = max(ws, hip.gram_flip_workspace_bytes(len(td["kinds"]), c, h, w))
                 if B > 1 and not self.independent:  # the dynamic term's (B C) x (B C) Gram over the whole window
                     self.gram_d[id(s)] = torch.empty(B * c, B * c, device=dev)
                     self.dmat_d[id(s)] = torch.empty(B * c, B * c, device=dev)
@@ -357,7 +429,8 @@ class StyleEngine:
         if plan.get("debug_poison") == "1":  # tests: every buffer starts as NaN, so a read-before-write shows up
             for t in list(self.act.values()) + list(self.gbuf.values()) + list(self.gram.values()) + list(self.dmat.values()) + \
                     list(self.gram_d.values()) + list(self.dmat_d.values()) + [self.mean[k] for k in self.guided] + \
-                    [t for gd in self.guided.values() for t in (gd["loss_scale"], gd["grad_scale"])]:
+                    [t for gd in self.guided.values() for t in (gd["loss_scale"], gd["grad_scale"])] + \
+                    [td[k] for td in self.term_steps.values() for k in ("s_gram", "s_dmat", "f_gram", "f_dmat")]:
                 if t is not None and not t.is_meta:
                     t.fill_(float("nan"))
             self.ws[:self.ws.numel() // 4 * 4].view(torch.float32)[:] = float("nan")
@@ -389,6 +462,50 @@ class StyleEngine:
             self.ev_main = torch.cuda.Event()
             self.ev_side = [torch.cuda.Event() for _ in range(ns)]
         self._refresh_guided()
+        self._refresh_terms()
+
+    def _refresh_terms(self):
+        """Terms steps (every _prepare, so never inside a capture): the deltas in use - StyleLoss.shift_deltas_used prints once and is host
+        only -, the module's term targets gathered into the step's (terms, C, C) arrays (in place, whenever a target tensor is new or was
+        rewritten) and the coefficients of engine.term_coefficients.  Missing targets are remembered and raised by _active as the module
+        path raises them.  _graph_key covers all of it."""
+        for s in self.steps:
+            td = getattr(self, "term_steps", {}).get(id(s))
+            if td is None:
+                continue
+            m = s.mod
+            c, h, w = td["chw"]
+            td["err"], shifts, srcs, factors_s = None, [], [], []
+            if td["s_target"] is not None and m.shift_factor > 0:
+                try:
+                    use = m.shift_deltas_used(h, w)
+                except RuntimeError as e:  # "... shift targets not captured"
+                    td["err"], use = str(e), []
+                for d in use:
+                    at = m.shift_target_deltas.index(d)
+                    shifts += [(0, d), (1, d)]
+                    srcs += [m.shift_targets_x[at], m.shift_targets_y[at]]
+                    factors_s += [m.shift_factor, m.shift_factor]
+            srcf, factors_f = [], []
+            if td["kinds"]:
+                missing = [k for k in td["kinds"] if k not in m.flip_targets]
+                if missing:
+                    td["err"] = td["err"] or f"{getattr(m, 'name', 'StyleLoss')}: mirror targets not captured (kinds {missing})"
+                else:
+                    srcf = [m.flip_targets[k] for k in td["kinds"]]
+                    factors_f = [m.rotation_factor if k == loss_mod.MIRROR_180 else m.flip_factor for k in td["kinds"]]
+            sig = tuple((t.data_ptr(), tuple(t.shape), t._version) for t in srcs + srcf)
+            if sig != td["sig"]:
+                for i, t in enumerate(srcs):
+                    td["s_target"][i].copy_(t)
+                for i, t in enumerate(srcf):
+                    td["f_target"][i].copy_(t)
+                td["sig"] = sig
+            td["shifts"] = shifts
+            ls, gs = term_coefficients(m.strength, m.normalize, c, factors_s)
+            lf, gf = term_coefficients(m.strength, m.normalize, c, factors_f)
+            td["coef"] = (tuple(ls), tuple(gs), tuple(1.0 / (c * loss_mod.shift_pairs(a, d, h, w)) for a, d in shifts),
+                          tuple(lf), tuple(gf), tuple(1.0 / (c * h * w) for _ in srcf))
 
     def _refresh_guided(self):
         """Guided steps (every _prepare, so never inside a capture): the module's layer guides and targets as they are now - both cached on
@@ -463,7 +580,14 @@ class StyleEngine:
                         or w.shape[1] not in (1, shapes_src[1]):
                     raise UnsupportedNet("weighted ContentLoss of this shape runs on the module path")
             return True
-        if m.mirror_kinds():  # (set after the plan was made: no engine evaluation without the mirror terms)
+        td = getattr(self, "term_steps", {}).get(id(s)) if getattr(m, "terms_engine", False) else None
+        if td is not None:
+            if getattr(m, "guide", None) is not None:  # (as loss.StyleLoss.forward)
+                raise NotImplementedError("StyleLoss: guides and shift_factor / flip_factor / rotation_factor > 0 together are not implemented")
+            if td["err"] is not None:
+                raise RuntimeError(td["err"])
+        if m.mirror_kinds() and (td is None or tuple(m.mirror_kinds()) != td["kinds"]):
+            # (`terms_engine` off, or set after the plan was made: no engine evaluation without the mirror terms)
             raise UnsupportedNet("mirrored StyleLoss runs on the module path")
         if getattr(m, "guide", None) is not None:
             gd = getattr(self, "guided", {}).get(id(s)) if plan.on("guided_engine") else None
@@ -474,7 +598,8 @@ class StyleEngine:
                     raise RuntimeError(f"{getattr(m, 'name', 'StyleLoss')}: guided style target not captured")
                 raise ValueError("guided StyleLoss: content and style guides must name the same regions")
             return True
-        if m.shift_factor > 0:  # (set after the plan was made: no engine evaluation without the shift terms)
+        if m.shift_factor > 0 and not getattr(m, "terms_engine", False):
+            # (`terms_engine` on: _prepare re-plans when the factor comes or goes; a map under 32 pixels has no shift term)
             raise UnsupportedNet("shifted StyleLoss runs on the module path")
         if m.target.nelement() == 0:
             raise RuntimeError(f"{m.name}: style target not captured")
@@ -622,6 +747,27 @@ class StyleEngine:
                     self._timed("gram_fwd", 2 * c * c * (n // c), n * 4 + r * c * c * 4, lambda: hip.gram_guided_fwd_mse_ledger(
                         f, lg.g, lg.scale, cov, lg.mass, self.gram[id(s)], self.mean[id(s)], gd["target"], self.dmat[id(s)], gd["loss_scale"],
                         gd["grad_scale"], self.ledger[0], s.slot, workspace=self.ws))
+            elif s.kind == "style" and id(s) in self.term_steps:
+                if self._active(s, a[s.src].shape):
+                    # the plain Gram matrix with today's coefficients into the module's own slot, then every shift's and every mirror's
+                    # matrix, D and loss - one record each in the step's hidden slots - on this stream, no whole-plane fusion
+                    f, td = a[s.src], self.term_steps[id(s)]
+                    c, n = f.shape[1], f[0].nelement()
+                    lw, gw = self._coefficients(s)
+                    ls, gs, ssc, lf, gf, fsc = td["coef"]
+                    self._timed("gram_fwd", 2 * c * c * (n // c), n * 4 + c * c * 4, lambda: hip.gram_fwd_mse_ledger(
+                        f, 1.0 / n, s.mod.use_covariance, self.gram[id(s)], self.mean[id(s)], s.mod.target, self.dmat[id(s)],
+                        lw / (c * c), gw * 4.0 / (c * c) / n, self.ledger[0], s.slot, workspace=self.ws))
+                    if td["shifts"]:
+                        k = len(td["shifts"])
+                        self._timed("gram_fwd", 2 * k * c * c * (n // c), n * 4 + 3 * k * c * c * 4, lambda: hip.gram_shift_fwd_mse_ledger(
+                            f, td["shifts"], ssc, None, td["s_gram"][:k], td["s_target"][:k], td["s_dmat"][:k], ls, gs, self.ledger[0],
+                            td["shift_slot"], workspace=self.ws))
+                    if lf:
+                        k = len(lf)
+                        self._timed("gram_fwd", 2 * k * c * c * (n // c), n * 4 + 3 * k * c * c * 4, lambda: hip.gram_flip_fwd_mse_ledger(
+                            f, td["kinds"], fsc, self.mean[id(s)], td["f_gram"], td["f_target"], td["f_dmat"], lf, gf, self.ledger[0],
+                            td["flip_slot"], workspace=self.ws))
             elif s.kind == "style" and self.independent and a[s.src].shape[0] > 1 and self._active(s, a[s.src].shape):
                 f = a[s.src]
                 c, n = f.shape[1], f[0].nelement()
@@ -859,6 +1005,22 @@ class StyleEngine:
                         lg = self.guided[id(s)]["lg"]
                         self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + lg.g.shape[0] * c * c * 4, lambda: hip.gram_guided_bwd_masked(
                             self.dmat[id(s)], f, lg.g, lg.scale, self.mean[id(s)], g[s.src], acc, relu_mask=rm))
+                    elif id(s) in self.term_steps:
+                        # up to three launches into the same gradient map: the first one writes (or joins what is there), the others
+                        # accumulate, and only the last one takes the ReLU mask - it then drops what the others left where a <= 0
+                        td = self.term_steps[id(s)]
+                        _, _, ssc, lf, _, fsc = td["coef"]
+                        k = len(td["shifts"])
+                        todo = [lambda ac, mk: hip.gram_bwd(self.dmat[id(s)], f, self.mean[id(s)], g[s.src], ac, workspace=self.ws, relu_mask=mk)]
+                        if k:
+                            todo.append(lambda ac, mk: hip.gram_shift_bwd_masked(td["s_dmat"][:k], f, td["shifts"], ssc, None, g[s.src], ac,
+                                                                                 relu_mask=mk))
+                        if lf:
+                            todo.append(lambda ac, mk: hip.gram_flip_bwd_masked(td["f_dmat"], f, td["kinds"], fsc, self.mean[id(s)], g[s.src],
+                                                                                ac, relu_mask=mk))
+                        for i, fn in enumerate(todo):
+                            self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + c * c * 4,
+                                        lambda: fn(acc or i > 0, rm if i == len(todo) - 1 else None))
                     else:
                         self._timed("gram_bwd", 2 * c * c * (n // c), n * 4 * 3 + c * c * 4, lambda: hip.gram_bwd(
                             self.dmat[id(s)], f, self.mean[id(s)], g[s.src], acc, workspace=self.ws, relu_mask=rm))
@@ -942,6 +1104,14 @@ class StyleEngine:
             hip.fill_(g[0], 0.0)
         if self.ledger is not None:  # (B == 1 or independent frames: no per-module terms to fold afterwards)
             hip.loss_ledger_sum(self.ledger, self.slots_all, self.total, self.slots_f64)
+            for s in self.steps:  # terms steps: a module's reported loss is its plain Gram term plus its terms (the total has them once)
+                td = self.term_steps.get(id(s))
+                if td is not None and self._active(s, a[s.src].shape):
+                    for e in (td["shift_slot"], td["flip_slot"]):
+                        if e is not None:
+                            self.slots_all[s.slot:s.slot + 1].add_(self.slots_all[e:e + 1])
+                            if self.slots_f64 is not None:
+                                self.slots_f64.view(-1)[s.slot:s.slot + 1].add_(self.slots_f64.view(-1)[e:e + 1])
             return
         if indep:
             for b in range(x.shape[0]):
@@ -1009,6 +1179,11 @@ class StyleEngine:
                 if gd is not None:  # a guided step: its guides, layer guides, targets (addresses) and coefficient arrays (values)
                     lg = gd["lg"]
                     key.append(("guided", sig(getattr(m, "guide", None)), sig(lg.g), sig(lg.scale), sig(lg.mass), sig(gd["target"]), gd["coef"]))
+                td = getattr(self, "term_steps", {}).get(id(s))
+                key.append(("terms_engine", bool(getattr(m, "terms_engine", False))))
+                if td is not None:  # a terms step: its targets (addresses), deltas, kinds, factors and coefficients (host launch arguments)
+                    key.append(("terms", td["sig"] and tuple(p[:2] for p in td["sig"]), tuple(td["shifts"]), td["kinds"], float(m.shift_factor),
+                                float(m.flip_factor), float(m.rotation_factor), td["coef"], td["err"]))
             elif s.kind == "conv":
                 key.append((id(m), m.weight.data_ptr(), m.weight._version))
         key.append(("hint", self.batch_hint, self.independent))

@@ -86,6 +86,12 @@ SIGNATURES = {
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
+    "maua_shift_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
+    "maua_shift_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "maua_shift_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_flip_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
+    "maua_flip_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "maua_flip_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_tv_fwd_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p, c_p, c_sz, c_p]),
     "maua_fill": (c_i, [c_p, c_i64, c_f, c_p]),
     "maua_depth_to_space": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -1050,6 +1056,92 @@ def gram_guided_bwd_masked(d_sym, f, guides, coef, mean, gf, accumulate, relu_ma
                                              _ptr(_f32(mean, "mean")), _ptr(_f32(relu_mask, "relu_mask")), _ptr(_f32(gf, "gf")), r, c, hw,
                                              int(accumulate), _stream()), "maua_guided_gram_bwd_masked")
     return gf
+
+
+def _f64_args(name, n, *lists):
+    """Host coefficient lists of n entries each -> ctypes double arrays."""
+    for v in lists:
+        if len(v) != n:
+            raise HipError(f"{name}: {len(v)} coefficients for {n} terms")
+    return [(ctypes.c_double * n)(*[float(x) for x in v]) for v in lists]
+
+
+def gram_shift_mse_ledger_supported(shifts, c):
+    """Do the partial sums of gram_shift_fwd_mse_ledger's finishing launch fit one ledger record?  (maua_hip.h states the bound.)"""
+    return bool(lib().maua_shift_gram_mse_ledger_supported(int(shifts), int(c)))
+
+
+def gram_shift_fwd_mse_ledger(f, shifts, scales, mean, out, target, dmat, loss_scales, grad_scales, ledger, slot, workspace=None):
+    """gram_shift_fwd into `out` (S,C,C) - the same bits - plus dmat[s] = grad_scales[s] (G_s - target[s]) (as it is, not symmetrised; zeros
+    where grad_scales[s] is 0) and sum_s loss_scales[s] sum (G_s - target[s])^2 as record `slot` of `ledger` (one frame's records).
+    loss_scales, grad_scales: one host float per shift."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(shifts)
+    if f.numel() != c * h * w or (mean is not None and mean.numel() != c):
+        raise HipError("gram_shift_fwd_mse_ledger: f is one (C, H, W) map and mean holds C values")
+    if out.numel() != n * c * c or target.numel() != n * c * c or dmat.numel() != n * c * c:
+        raise HipError("gram_shift_fwd_mse_ledger: gram, target and dmat are (S, C, C)")
+    axes, deltas, fac = _shift_args(shifts, scales)
+    ls, gs = _f64_args("gram_shift_fwd_mse_ledger", n, loss_scales, grad_scales)
+    workspace = _ws(workspace, gram_shift_workspace_bytes(n, c, h, w), f.device)
+    _check(lib().maua_shift_gram_fwd_mse_ledger(
+        _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), axes, deltas, fac, _ptr(_f32(out, "gram")), n, c, h, w, _ptr(_f32(target, "target")), ls, gs,
+        _ptr(_f32(dmat, "dmat")), ledger.data_ptr(), int(slot), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+        "maua_shift_gram_fwd_mse_ledger")
+    return out
+
+
+def gram_shift_bwd_masked(d, f, shifts, coefs, mean, gx, accumulate, relu_mask=None):
+    """gram_shift_bwd whose result is written as 0 where relu_mask (shaped like gx) is <= 0; None: gram_shift_bwd's bits."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(shifts)
+    if f.numel() != c * h * w or d.numel() != n * c * c or gx.numel() != f.numel() or (mean is not None and mean.numel() != c) or \
+            (relu_mask is not None and relu_mask.numel() != gx.numel()):
+        raise HipError("gram_shift_bwd_masked: shapes of d, f, mean, relu_mask and gx do not agree")
+    axes, deltas, fac = _shift_args(shifts, coefs)
+    _check(lib().maua_shift_gram_bwd_masked(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), axes, deltas, fac,
+                                            _ptr(_f32(relu_mask, "relu_mask")), _ptr(_f32(gx, "gx")), n, c, h, w, int(accumulate), _stream()),
+           "maua_shift_gram_bwd_masked")
+    return gx
+
+
+def gram_flip_mse_ledger_supported(mirrors, c):
+    """Do the partial sums of gram_flip_fwd_mse_ledger's finishing launch fit one ledger record?  (maua_hip.h states the bound.)"""
+    return bool(lib().maua_flip_gram_mse_ledger_supported(int(mirrors), int(c)))
+
+
+def gram_flip_fwd_mse_ledger(f, kinds, scales, mean, out, target, dmat, loss_scales, grad_scales, ledger, slot, workspace=None):
+    """gram_flip_fwd into `out` (M,C,C) - the same bits - plus dmat[m] = grad_scales[m] (G_m - target[m]) (bit-symmetric; zeros where
+    grad_scales[m] is 0) and sum_m loss_scales[m] sum (G_m - target[m])^2 as record `slot` of `ledger` (one frame's records).
+    loss_scales, grad_scales: one host float per mirror."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(kinds)
+    if f.numel() != c * h * w or (mean is not None and mean.numel() != c):
+        raise HipError("gram_flip_fwd_mse_ledger: f is one (C, H, W) map and mean holds C values")
+    if out.numel() != n * c * c or target.numel() != n * c * c or dmat.numel() != n * c * c:
+        raise HipError("gram_flip_fwd_mse_ledger: gram, target and dmat are (M, C, C)")
+    kd, fac = _flip_args(kinds, scales)
+    ls, gs = _f64_args("gram_flip_fwd_mse_ledger", n, loss_scales, grad_scales)
+    workspace = _ws(workspace, gram_flip_workspace_bytes(n, c, h, w), f.device)
+    _check(lib().maua_flip_gram_fwd_mse_ledger(
+        _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), kd, fac, _ptr(_f32(out, "gram")), n, c, h, w, _ptr(_f32(target, "target")), ls, gs,
+        _ptr(_f32(dmat, "dmat")), ledger.data_ptr(), int(slot), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+        "maua_flip_gram_fwd_mse_ledger")
+    return out
+
+
+def gram_flip_bwd_masked(d, f, kinds, coefs, mean, gx, accumulate, relu_mask=None):
+    """gram_flip_bwd whose result is written as 0 where relu_mask (shaped like gx) is <= 0; None: gram_flip_bwd's bits."""
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    n = len(kinds)
+    if f.numel() != c * h * w or d.numel() != n * c * c or gx.numel() != f.numel() or (mean is not None and mean.numel() != c) or \
+            (relu_mask is not None and relu_mask.numel() != gx.numel()):
+        raise HipError("gram_flip_bwd_masked: shapes of d, f, mean, relu_mask and gx do not agree")
+    kd, fac = _flip_args(kinds, coefs)
+    _check(lib().maua_flip_gram_bwd_masked(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), kd, fac,
+                                           _ptr(_f32(relu_mask, "relu_mask")), _ptr(_f32(gx, "gx")), n, c, h, w, int(accumulate), _stream()),
+           "maua_flip_gram_bwd_masked")
+    return gx
 
 
 def mse_fwd_bwd(x, target, grad, loss_scale, grad_scale, accumulate, loss_out, workspace=None, mask_grad_by_x=False):

@@ -323,6 +323,10 @@ class StyleLoss(nn.Module):
         self.shift_factor = shift_factor
         self.flip_factor = flip_factor
         self.rotation_factor = rotation_factor
+        # (not a constructor argument: the reference has none) True: a module with shift or mirror terms is evaluated by engine.StyleEngine
+        # ("terms steps") instead of sending the whole network to the module path; models.py sets it from the preset
+        # key `terms_engine`
+        self.terms_engine = False
         self.gram = GramMatrix()
         self.crit = _MseFn.apply
         self.loss = 0

@@ -773,6 +773,8 @@ def assemble(features, layer_list, args):
                           # preset keys (--load_args), not flags: the reference's flag surface has neither
                           flip_factor=float(getattr(args, "flip_factor", 0) or 0), rotation_factor=float(getattr(args, "rotation_factor", 0) or 0)),
                 "style", style_losses)
+            # preset key too: the shift / mirror terms of this module run inside the fused engine (engine.py "terms steps"), default off
+            style_losses[-1].terms_engine = bool(int(getattr(args, "terms_engine", 0) or 0))
             found_style = True
         return found_content, found_style
 

@@ -65,6 +65,18 @@ def _mirrored(net_or_losses):
     return any(isinstance(m, loss_mod.StyleLoss) and bool(m.mirror_kinds()) for m in mods)
 
 
+def _terms_on_module_path(net_or_losses):
+    """The reason a shifted or mirrored network stays on the module path, or None: a style module with shift_factor > 0, or with a mirror
+    in use, whose `terms_engine` is off (the default).  With it on the fused engine evaluates those terms (engine.py, "terms steps")."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    style = [m for m in mods if isinstance(m, loss_mod.StyleLoss) and not getattr(m, "terms_engine", False)]
+    if _shifted(style):
+        return "shifted StyleLoss runs on the module path"
+    if _mirrored(style):
+        return "mirrored StyleLoss runs on the module path"
+    return None
+
+
 def _style_targets_missing(net):
     """A style module without its target - or, with shift_factor > 0, without its shift targets, or with a mirror in use without that
     mirror's target (the factor was set after the capture)."""
@@ -76,10 +88,10 @@ def _engine_of(net):
     """The fused engine of a loss network (built once per network; None when its module layout is not covered)."""
     if _guided(net) and not plan.on("guided_engine"):
         return None  # (not remembered: the same network without guides takes the engine again)
-    if _shifted(net):
-        return None  # (not remembered either: the same network with shift_factor 0 takes the engine again)
-    if _mirrored(net):
-        return None  # (nor this: with flip_factor and rotation_factor back at 0 the network takes the engine again)
+    if _terms_on_module_path(net) is not None:
+        # (not remembered either: the same network with shift_factor, flip_factor and rotation_factor back at 0 - or with `terms_engine`
+        #  set on its style modules - takes the engine again)
+        return None
     eng = getattr(net, "_maua_engine", None)
     if eng is None and not getattr(net, "_maua_engine_refused", False):
         if not all(hasattr(net, a) for a in ("content_losses", "style_losses", "tv_losses", "temporal_losses")):
@@ -218,10 +230,8 @@ class PixelOptimizer:
             # (also on the L-BFGS bundle path below: no engine, no bundle, no captured graph - unless the planner field guided_engine is on)
             if _guided(losses) and not plan.on("guided_engine"):
                 raise engine_mod.UnsupportedNet("guided StyleLoss runs on the module path")
-            if _shifted(losses):
-                raise engine_mod.UnsupportedNet("shifted StyleLoss runs on the module path")
-            if _mirrored(losses):
-                raise engine_mod.UnsupportedNet("mirrored StyleLoss runs on the module path")
+            if _terms_on_module_path(losses) is not None:  # (shift / mirror terms whose module has `terms_engine` off)
+                raise engine_mod.UnsupportedNet(_terms_on_module_path(losses))
             self.engine = getattr(net, "_maua_engine", None) or engine_mod.StyleEngine(net, losses)
             net._maua_engine = self.engine
         except engine_mod.UnsupportedNet:
@@ -243,7 +253,9 @@ class PixelOptimizer:
                                 int(args.lbfgs_num_correction), float(args.lbfgs_tolerance_change), float(args.lbfgs_tolerance_grad))
             try:
                 self.engine._prepare(self.x)  # (allocates for this shape if the engine last served another one: a new epoch)
-            except engine_mod.UnsupportedNet:  # (a guided layer the engine does not take, planner field guided_engine: module path)
+            except engine_mod.UnsupportedNet:  # (a guided or terms layer the engine does not take here: module path)
+                if self.independent:
+                    raise
                 self.engine, self._bundle_key = None, None
         if self._bundle_key is not None:
             bundle = self.engine.iter_graphs.get(self._bundle_key)
@@ -490,6 +502,8 @@ def optimize_frames(contents, styles, inits, num_iters, args, net, losses, plann
     eng = _engine_of(net)
     if eng is None:
         raise engine_mod.UnsupportedNet("frame batches need a network the fused engine covers")
+    if contents.shape[0] > 1 and (_shifted(net) or _mirrored(net)):  # (`terms_engine` on: the engine takes those terms for one frame only)
+        raise engine_mod.UnsupportedNet("shifted / mirrored StyleLoss on the engine: one frame per evaluation (B = 1)")
     hint = int(planned_frames) if planned_frames else int(contents.shape[0])
     eng.independent, eng.batch_hint = contents.shape[0] > 1, hint
     if not args.verbose:

@@ -6,7 +6,10 @@ Kernels: the five VGG-19 style-layer shapes of a 1024 x 1024 image (C x H_l x W_
   x4             hip.gram_shift_fwd / hip.gram_shift_bwd with one shift, delta 4 along x: the yardstick of the expectation below;
   LR / UD / 180  one mirror alone;
   LR+UD          the two mirrors of flip_factor in one call (what a StyleLoss with flip_factor > 0 and rotation_factor 0 launches);
-  all3           the three mirrors in one call.
+  all3           the three mirrors in one call;
+  LR+UD + mse    what the module path launches for flip_factor: hip.gram_flip_fwd and one hip.mse_fwd_bwd per matrix / hip.gram_flip_bwd;
+  LR+UD fused    what the fused engine launches (StyleLoss.terms_engine): hip.gram_flip_fwd_mse_ledger - matrices, D and the loss record from
+                 the finishing launch - / hip.gram_flip_bwd_masked with the ReLU mask in its epilogue.
 The expectation: a mirror reads the bytes one shift reads, computes the tile pairs on or above the diagonal only and has one run of
 backward stages where a shift has two, so it should not cost more than x4 of the same run and shape (`x x4` <= 1).
 The variants run interleaved, `--rounds` rounds of `--reps` back-to-back calls between device events after a warm-up round; the table gives
@@ -14,7 +17,8 @@ the median and the minimum over the rounds.  Feature maps are relu(randn): the s
 
 Job: VGG-19 (seeded synthetic weights), 1024 x 1024, default layers, L-BFGS: iterations per second of `--steps` steps after `--warmup` (host
 clock around a device synchronise) with flip_factor 0 on the fused engine (the project's normal route), flip_factor 0 on the module path
-(autograd over the HIP kernels) and flip_factor 1, rotation_factor 0 (module path: the only route of the mirror terms).
+(autograd over the HIP kernels), flip_factor 1, rotation_factor 0 on the module path (the default route of the mirror terms) and the same with
+the preset key terms_engine = 1 (the fused engine and its captured graph) - all in the same run.
 
     python tools/bench_flip.py [--rounds 7] [--reps 10] [--steps 20] [--warmup 3] [--size 1024] > profiles/bench_flip.md
 """
@@ -72,6 +76,24 @@ def kernel_table(a, out):
             keep.append((ws, grams, d))
             variants[label] = (M, lambda kinds=kinds, scales=scales, ws=ws, grams=grams: hip.gram_flip_fwd(f, kinds, scales, None, out=grams, workspace=ws),
                                lambda kinds=kinds, scales=scales, d=d: hip.gram_flip_bwd(d, f, kinds, scales, None, gf, False))
+            if label == "LR+UD":  # flip_factor's pair finished with the MSE: per matrix (module path) and in the finishing launch (engine)
+                target = torch.randn(M, C, C, generator=gen).cuda() / (C * C)
+                target, dm = (target + target.transpose(1, 2)).contiguous(), torch.empty(M, C, C, device="cuda")
+                one, led = torch.zeros(1, device="cuda"), hip.loss_ledger(1, 1, f.device)
+                ws_m = torch.empty(hip.reduce_workspace_bytes(C * C), dtype=torch.uint8, device="cuda")
+                ls, gs = [1.0 / (C * C)] * M, [2.0 / (C * C)] * M
+                keep.append((target, dm, one, led, ws_m))
+
+                def unfused(kinds=kinds, scales=scales, ws=ws, grams=grams, target=target, dm=dm, one=one, ws_m=ws_m, ls=ls, gs=gs):
+                    hip.gram_flip_fwd(f, kinds, scales, None, out=grams, workspace=ws)
+                    for i in range(len(kinds)):
+                        hip.mse_fwd_bwd(grams[i], target[i], dm[i], ls[i], gs[i], False, one, workspace=ws_m)
+
+                variants["LR+UD + mse"] = (M, unfused, variants[label][2])
+                variants["LR+UD fused"] = (M, lambda kinds=kinds, scales=scales, ws=ws, grams=grams, target=target, dm=dm, led=led, ls=ls, gs=gs:
+                                           hip.gram_flip_fwd_mse_ledger(f, kinds, scales, None, grams, target, dm, ls, gs, led[0], 0, workspace=ws),
+                                           lambda kinds=kinds, scales=scales, d=d: hip.gram_flip_bwd_masked(d, f, kinds, scales, None, gf, False,
+                                                                                                              relu_mask=f))
         times = {k: ([], []) for k in variants}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         for rnd in range(a.rounds + 1):  # round 0 warms up
@@ -114,10 +136,12 @@ def job_rates(a, out):
     S = a.size
     content, style, init = synth.images(S)
     rates = {}
-    for label, ff in (("flip_factor 0, fused engine", 0.0), ("flip_factor 0, module path", 0.0), ("flip_factor 1, rotation_factor 0 (module path)", 1.0)):
+    for label, ff, te in (("flip_factor 0, fused engine", 0.0, 0), ("flip_factor 0, module path", 0.0, 0),
+                          ("flip_factor 1, rotation_factor 0 (module path)", 1.0, 0),
+                          ("flip_factor 1, rotation_factor 0, terms_engine 1 (fused engine)", 1.0, 1)):
         preset = os.path.join(tmp, "sym.json")
         with open(preset, "w") as fh:
-            json.dump({"flip_factor": ff, "rotation_factor": 0.0}, fh)
+            json.dump({"flip_factor": ff, "rotation_factor": 0.0, "terms_engine": te}, fh)
         args = config.get_args(["--content", "c.png", "--style", "s.png", "--model_file", wfile, "--disable_check", "--scaling_args", scaling,
                                 "--image_sizes", str(S), "--num_iters", str(a.steps), "--seed", "0", "--no_hist_match", "--load_args", preset])
         optim.set_model_args(args, S)
@@ -130,6 +154,7 @@ def job_rates(a, out):
         if "module path" in label:
             opt.engine = None
         assert (opt.engine is not None) == ("fused" in label), label
+        assert bool(opt.engine is not None and opt.engine.term_steps) == bool(te), label
         for _ in range(a.warmup):
             opt.step()
         torch.cuda.synchronize()

@@ -4,13 +4,17 @@
 Kernels: the five VGG-19 style-layer shapes of a 1024 x 1024 image (C x H_l x W_l).  Per shape, forward and backward of
   base     hip.gram_fwd / hip.gram_bwd (the kernels every job runs: the baseline, never the new code);
   shifts   hip.gram_shift_fwd / hip.gram_shift_bwd with the layer's own shift list (loss.shift_deltas: every delta along x and y), in one call;
-  x4 / y4  one shift alone, delta 4 along x and along y (the cost of a single shifted product).
+  x4 / y4  one shift alone, delta 4 along x and along y (the cost of a single shifted product);
+  shifts + mse    what the module path launches for the layer's list: hip.gram_shift_fwd and one hip.mse_fwd_bwd per matrix / hip.gram_shift_bwd;
+  shifts fused    what the fused engine launches (StyleLoss.terms_engine): hip.gram_shift_fwd_mse_ledger - matrices, D and the loss record from
+                  the finishing launch - / hip.gram_shift_bwd_masked with the ReLU mask in its epilogue.
 The variants run interleaved, `--rounds` rounds of `--reps` back-to-back calls between device events after a warm-up round; the table gives
 the median and the minimum over the rounds.  Feature maps are relu(randn): the same data for every variant of a shape.
 
 Job: VGG-19 (seeded synthetic weights), 1024 x 1024, default layers, L-BFGS: iterations per second of `--steps` steps after `--warmup` (host
 clock around a device synchronise) with --shift_factor 0 on the fused engine (the project's normal route), --shift_factor 0 on the module
-path (autograd over the HIP kernels) and --shift_factor 1 (module path: the only route of the shift terms).
+path (autograd over the HIP kernels), --shift_factor 1 on the module path (the default route of the shift terms) and --shift_factor 1 with the
+preset key terms_engine = 1 (the fused engine and its captured graph) - all in the same run.
 
     python tools/bench_shift.py [--rounds 7] [--reps 10] [--steps 20] [--warmup 3] [--size 1024] > profiles/bench_shift.md
 """
@@ -62,6 +66,23 @@ def kernel_table(a, out):
             keep.append((ws, grams, d))
             variants[label] = (S, lambda shifts=shifts, scales=scales, ws=ws, grams=grams: hip.gram_shift_fwd(f, shifts, scales, None, out=grams, workspace=ws),
                                lambda shifts=shifts, scales=scales, d=d: hip.gram_shift_bwd(d, f, shifts, scales, None, gf, False))
+            if label == "shifts":  # the layer's list finished with the MSE: per matrix (module path) and in the finishing launch (engine)
+                target, dm = torch.randn(S, C, C, generator=gen).cuda() / (C * C), torch.empty(S, C, C, device="cuda")
+                one, led = torch.zeros(1, device="cuda"), hip.loss_ledger(1, 1, f.device)
+                ws_m = torch.empty(hip.reduce_workspace_bytes(C * C), dtype=torch.uint8, device="cuda")
+                ls, gs = [1.0 / (C * C)] * S, [2.0 / (C * C)] * S
+                keep.append((target, dm, one, led, ws_m))
+
+                def unfused(shifts=shifts, scales=scales, ws=ws, grams=grams, target=target, dm=dm, one=one, ws_m=ws_m, ls=ls, gs=gs):
+                    hip.gram_shift_fwd(f, shifts, scales, None, out=grams, workspace=ws)
+                    for i in range(len(shifts)):
+                        hip.mse_fwd_bwd(grams[i], target[i], dm[i], ls[i], gs[i], False, one, workspace=ws_m)
+
+                variants["shifts + mse"] = (S, unfused, variants[label][2])
+                variants["shifts fused"] = (S, lambda shifts=shifts, scales=scales, ws=ws, grams=grams, target=target, dm=dm, led=led, ls=ls, gs=gs:
+                                            hip.gram_shift_fwd_mse_ledger(f, shifts, scales, None, grams, target, dm, ls, gs, led[0], 0, workspace=ws),
+                                            lambda shifts=shifts, scales=scales, d=d: hip.gram_shift_bwd_masked(d, f, shifts, scales, None, gf, False,
+                                                                                                                  relu_mask=f))
         times = {k: ([], []) for k in variants}
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         for rnd in range(a.rounds + 1):  # round 0 warms up
@@ -98,9 +119,14 @@ def job_rates(a, out):
     S = a.size
     content, style, init = synth.images(S)
     rates = {}
-    for label, sf in (("--shift_factor 0, fused engine", "0"), ("--shift_factor 0, module path", "0"), ("--shift_factor 1 (module path)", "1")):
+    for label, sf, te in (("--shift_factor 0, fused engine", "0", 0), ("--shift_factor 0, module path", "0", 0), ("--shift_factor 1 (module path)", "1", 0),
+                          ("--shift_factor 1, terms_engine 1 (fused engine)", "1", 1)):
+        preset = os.path.join(tmp, "terms.json")
+        with open(preset, "w") as fh:
+            json.dump({"terms_engine": te}, fh)
         args = config.get_args(["--content", "c.png", "--style", "s.png", "--model_file", wfile, "--disable_check", "--scaling_args", scaling,
-                                "--image_sizes", str(S), "--num_iters", str(a.steps), "--seed", "0", "--no_hist_match", "--shift_factor", sf])
+                                "--image_sizes", str(S), "--num_iters", str(a.steps), "--seed", "0", "--no_hist_match", "--shift_factor", sf,
+                                "--load_args", preset])
         optim.set_model_args(args, S)
         net, losses = models.load_model(args)
         optim.set_content_targets(net, content, args)
@@ -111,6 +137,7 @@ def job_rates(a, out):
         if "module path" in label:
             opt.engine = None
         assert (opt.engine is not None) == ("fused" in label), label
+        assert bool(opt.engine is not None and opt.engine.term_steps) == bool(te), label
         for _ in range(a.warmup):
             opt.step()
         torch.cuda.synchronize()
