@@ -417,6 +417,34 @@ int maua_gram_flip_fwd(const float* f, const float* mean, const int* kinds, cons
 int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const int* kinds, const double* coefs, float* gx, int mirrors, int c,
                        int h, int w, int accumulate, maua_stream_t stream);
 
+/* ---- feature-histogram style loss: each channel histogram-matched to the style's quantiles (feat_hist.hip) ------- */
+/* Risser, Wilmot & Barnes 2017.  One frame f[C][h w] (N = h w), a target table[C][knots] (fp32, non-decreasing along a row: the style
+ * channel's quantiles at (k + 0.5) / knots), `bins` histogram bins.  Per channel c:
+ *     lo = min f[c], hi = max f[c] (exact);  inv = (float)((double)bins / ((double)hi - (double)lo)), 0 where hi == lo;
+ *     t = fl32(fl32(v - lo) * inv) (one fp32 subtraction, one fp32 multiplication, not contracted), b = min(bins - 1, (int)t),
+ *     frac = min(1, fl32(t - b));  cnt[b] = number of elements of bin b, cum = its exclusive prefix sum (integers);
+ *     q = (cum[b] + frac cnt[b]) / N,  p = clamp(q knots - 0.5, 0, knots - 1),  i0 = min(knots - 2, floor(p)),
+ *     R = table[c][i0] + (p - i0) (table[c][i0 + 1] - table[c][i0])    (fp32);    loss = sum over c, i of (f - R)^2 / (C N).
+ * state: maua_feat_hist_state_bytes(C, bins) bytes, per channel a record of bins + 3 four-byte words:
+ *     word 0: lo (fp32), word 1: hi (fp32), words 2 .. bins + 2: cum[0 .. bins] (int32), cum[bins] = N.
+ * maua_feat_hist_fwd fills `state` and writes loss[0] (device, fp32): five launches that read f three times (range, counts, residual)
+ *   and write nothing of size C N.  Per-workgroup histograms are counted in LDS and merged into `state` with integer global atomics; the
+ *   partial sums of (f - R)^2 go to the workspace and one finishing workgroup adds them in a fixed order in fp64.  No float atomics: the
+ *   same inputs give the same bits.  workspace: maua_feat_hist_workspace_bytes(C, h, w, bins, knots) bytes, 8-byte aligned.
+ * maua_feat_hist_bwd: gx[C][h w] (+)= coef * upstream[0] * (f - R), R recomputed from `state` as maua_feat_hist_fwd left it for the same f
+ *   and table (R is a constant in the derivative).  upstream: device fp32 scalar, NULL counts as 1; coef: host double.  With
+ *   accumulate == 0 every element of gx is written.  One launch, no workspace; f is read once, gx written once.
+ * No element outside f, table and state is read.  1 <= C <= 65536, h, w >= 1 with h w < 2^30, 16 <= bins <= 1024, 2 <= knots <= 4096;
+ * anything else returns MAUA_E_UNSUPPORTED (the queries: 0), null pointers MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before
+ * any launch. */
+int maua_feat_hist_supported(int c, int h, int w, int bins, int knots);
+size_t maua_feat_hist_workspace_bytes(int c, int h, int w, int bins, int knots);
+size_t maua_feat_hist_state_bytes(int c, int bins);
+int maua_feat_hist_fwd(const float* f, const float* table, void* state, float* loss, int c, int h, int w, int bins, int knots, void* workspace,
+                       size_t workspace_bytes, maua_stream_t stream);
+int maua_feat_hist_bwd(const float* f, const float* table, const void* state, const float* upstream, double coef, float* gx, int c, int h, int w,
+                       int bins, int knots, int accumulate, maua_stream_t stream);
+
 /* ---- shifted and mirrored Gram terms of the fused engine (gram_shift.hip, gram_flip.hip) ------------------------ */
 /* The two forward passes above with the MSE against per-term targets formed by their finishing launch, and the two backward passes with a
  * ReLU mask in their epilogue.  Arguments, limits and return codes are those of maua_gram_shift_fwd / _bwd and maua_gram_flip_fwd / _bwd;

@@ -121,6 +121,8 @@ class StyleEngine:
                     raise UnsupportedNet("shifted StyleLoss runs on the module path")
                 if m.mirror_kinds() and not getattr(m, "terms_engine", False):
                     raise UnsupportedNet("mirrored StyleLoss runs on the module path")
+                if getattr(m, "hist_loss_factor", 0) > 0:  # (whatever `terms_engine` says: there is no feature-histogram step)
+                    raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -580,6 +582,8 @@ class StyleEngine:
                         or w.shape[1] not in (1, shapes_src[1]):
                     raise UnsupportedNet("weighted ContentLoss of this shape runs on the module path")
             return True
+        if getattr(m, "hist_loss_factor", 0) > 0:  # (set after the engine was built: no engine evaluation without the term)
+            raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
         td = getattr(self, "term_steps", {}).get(id(s)) if getattr(m, "terms_engine", False) else None
         if td is not None:
             if getattr(m, "guide", None) is not None:  # (as loss.StyleLoss.forward)

@@ -83,6 +83,11 @@ SIGNATURES = {
     "maua_gram_flip_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "maua_gram_flip_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "maua_gram_flip_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_feat_hist_supported": (c_i, [c_i, c_i, c_i, c_i, c_i]),
+    "maua_feat_hist_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    "maua_feat_hist_state_bytes": (c_sz, [c_i, c_i]),
+    "maua_feat_hist_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_feat_hist_bwd": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
@@ -1016,6 +1021,80 @@ def gram_flip_bwd(d, f, kinds, coefs, mean, gx, accumulate):
     kd, fac = _flip_args(kinds, coefs)
     _check(lib().maua_gram_flip_bwd(_ptr(_f32(d, "d")), _ptr(_f32(f, "f")), _ptr(_f32(mean, "mean")), kd, fac, _ptr(_f32(gx, "gx")),
                                     n, c, h, w, int(accumulate), _stream()), "maua_gram_flip_bwd")
+    return gx
+
+
+def feat_hist_supported(c, h, w, bins, knots):
+    return bool(lib().maua_feat_hist_supported(int(c), int(h), int(w), int(bins), int(knots)))
+
+
+def feat_hist_workspace_bytes(c, h, w, bins, knots):
+    return lib().maua_feat_hist_workspace_bytes(int(c), int(h), int(w), int(bins), int(knots))
+
+
+def feat_hist_state_bytes(c, bins):
+    return lib().maua_feat_hist_state_bytes(int(c), int(bins))
+
+
+def feat_hist_quantiles(f, knots):
+    """The target table of one style frame f (1,C,H,W) or (C,H,W): per channel the sorted activation s[0 .. N - 1] read at
+    min(N - 1, floor((k + 0.5) N / knots)), k = 0 .. knots - 1 -> (C, knots) float32, non-decreasing along a row.  Sort and gather on the
+    device (torch.sort): this runs once per style image and scale, not per iteration."""
+    c = f.shape[-3]
+    n = f.shape[-2] * f.shape[-1]
+    if f.numel() != c * n or not 2 <= int(knots) <= 4096:
+        raise HipError("feat_hist_quantiles: f is one (C, H, W) map and 2 <= knots <= 4096")
+    if not f.is_cuda:
+        raise HipError("feat_hist_quantiles: a ROCm device tensor is needed (there is no CPU path)")
+    k = int(knots)
+    at = torch.tensor([min(n - 1, ((2 * i + 1) * n) // (2 * k)) for i in range(k)], dtype=torch.int64, device=f.device)
+    return torch.sort(_f32(f, "f").reshape(c, n), dim=1).values.index_select(1, at).contiguous()
+
+
+def feat_hist_state_parts(state, c, bins):
+    """(lo (C,) float32, hi (C,) float32, cum (C, bins + 1) int32) of a state maua_feat_hist_fwd filled (the layout of maua_hip.h)."""
+    rec = state.view(torch.int32)[:c * (bins + 3)].reshape(c, bins + 3)
+    ends = rec[:, :2].contiguous().view(torch.float32)
+    return ends[:, 0], ends[:, 1], rec[:, 2:]
+
+
+def _feat_hist_dims(who, f, table, bins):
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    if f.numel() != c * h * w or table.dim() != 2 or table.shape[0] != c:
+        raise HipError(f"{who}: f is one (C, H, W) map and table is (C, knots)")
+    knots = table.shape[1]
+    if not feat_hist_supported(c, h, w, bins, knots):
+        raise HipError(f"{who}: {c} channels, {h} x {w} pixels, {bins} bins, {knots} knots are not supported")
+    return c, h, w, knots
+
+
+def feat_hist_fwd(f, table, bins, state=None, loss=None, workspace=None):
+    """f: (1,C,H,W) or (C,H,W); table: (C, knots).  Returns (loss (1,) float32 = mean (f - R)^2 with R the histogram-matched map, state):
+    `state` (int32 words, feat_hist_state_bytes) holds lo, hi and the cumulative counts per channel - feat_hist_bwd reads it."""
+    c, h, w, knots = _feat_hist_dims("feat_hist_fwd", f, table, bins)
+    words = feat_hist_state_bytes(c, bins) // 4
+    if state is None:
+        state = torch.empty(words, dtype=torch.int32, device=f.device)
+    elif state.dtype != torch.int32 or state.numel() < words or not state.is_contiguous() or not state.is_cuda:
+        raise HipError("feat_hist_fwd: state is a contiguous int32 device tensor of feat_hist_state_bytes")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=f.device)
+    workspace = _ws(workspace, feat_hist_workspace_bytes(c, h, w, bins, knots), f.device)
+    _check(lib().maua_feat_hist_fwd(_ptr(_f32(f, "f")), _ptr(_f32(table, "table")), state.data_ptr(), _ptr(_f32(loss, "loss")), c, h, w,
+                                    int(bins), knots, workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+           "maua_feat_hist_fwd")
+    return loss, state
+
+
+def feat_hist_bwd(f, table, state, bins, coef, gx, accumulate, upstream=None):
+    """gx (+)= coef upstream (f - R); state: what feat_hist_fwd left for the same f and table; upstream: device float32 scalar or None (1)."""
+    c, h, w, knots = _feat_hist_dims("feat_hist_bwd", f, table, bins)
+    if gx.numel() != f.numel() or state.dtype != torch.int32 or state.numel() < feat_hist_state_bytes(c, bins) // 4 or not state.is_cuda \
+            or (upstream is not None and upstream.numel() != 1):
+        raise HipError("feat_hist_bwd: shapes of f, state, upstream and gx do not agree")
+    _check(lib().maua_feat_hist_bwd(_ptr(_f32(f, "f")), _ptr(_f32(table, "table")), state.data_ptr(), _ptr(_f32(upstream, "upstream")),
+                                    float(coef), _ptr(_f32(gx, "gx")), c, h, w, int(bins), knots, int(accumulate), _stream()),
+           "maua_feat_hist_bwd")
     return gx
 
 

@@ -20,6 +20,10 @@ activation with translated copies of itself (csrc/gram_shift.hip, DESIGN.md sect
 Symmetry (the same paper's other half): with `flip_factor > 0` a StyleLoss also matches the products of the activation with its left-right
 and its up-down mirror image, with `rotation_factor > 0` the product with its point mirror (rotation by 180 degrees; csrc/gram_flip.hip,
 DESIGN.md section 13).  Module path only, like the shift terms.
+
+Feature histograms (Risser, Wilmot & Barnes 2017): with `hist_loss_factor > 0` a StyleLoss also histogram-matches every channel of the
+activation to the style's channel and adds the mean squared distance to the matched map (csrc/feat_hist.hip) - the
+one term here that is not a second-order statistic.  Module path only.
 """
 import sys
 
@@ -209,6 +213,30 @@ class _FlipGramFn(torch.autograd.Function):
         return gx, None, None, None
 
 
+class _FeatHistFn(torch.autograd.Function):
+    """h = mean (x - R)^2 for one frame x (1, C, H, W): R is x histogram-matched, channel by channel, to the quantile table `table`
+    (C, knots) over `bins` bins (hip.feat_hist_fwd).  R is a constant in the derivative: backward is 2 (x - R) / (C H W) times the incoming
+    gradient, which hip.feat_hist_bwd reads on the device."""
+
+    @staticmethod
+    def forward(ctx, x, table, bins):
+        B, C, H, W = x.shape
+        if B != 1:
+            raise ValueError("feature histograms: one frame per call (B = 1)")
+        xc = x.contiguous()
+        loss, state = hip.feat_hist_fwd(xc, table, int(bins))
+        ctx.save_for_backward(xc, table, state)
+        ctx.bins = int(bins)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, table, state = ctx.saved_tensors
+        gx = torch.empty_like(xc)
+        hip.feat_hist_bwd(xc, table, state, ctx.bins, 2.0 / xc.numel(), gx, False, upstream=g.reshape(1).float().contiguous())
+        return gx, None, None
+
+
 class LayerGuides:
     """The guides of one style layer: `g` (R, H_l W_l) = the image-resolution guides resized to the activation with the project's bilinear
     kernel, `mass` N_r = sum g_r^2 (device, fp64; `mass_host` its one read-back), `active` = [N_r >= 1] and `scale` = 1 / (C N_r) on the
@@ -310,8 +338,9 @@ class StyleLoss(nn.Module):
 
     Per frame the static scalar t = mse(G, T) becomes t + shift_factor sum_s mse(G_s, T_s) + flip_factor (mse(G_LR, T_LR) + mse(G_UD, T_UD))
     + rotation_factor mse(G_180, T_180): the shifted products of DESIGN.md section 12 and the mirrored ones of section 13.  `rotation_factor`
-    drives the 180 degree term only; the paper's 90 degree terms (square maps, a transposing read) are not implemented.  The dynamic term
-    gets neither."""
+    drives the 180 degree term only; the paper's 90 degree terms (square maps, a transposing read) are not implemented.  With
+    `hist_loss_factor > 0` the scalar also gains hist_loss_factor h, h the feature-histogram term of DESIGN.md section 15 (`hist_loss_bins`
+    bins, a target of `hist_loss_knots` quantiles per channel; use_covariance does not change it).  The dynamic term gets none of these."""
 
     def __init__(self, strength, use_covariance=False, normalize=False, video_style_factor=0, shift_factor=0,
                  flip_factor=0, rotation_factor=0):
@@ -327,6 +356,10 @@ class StyleLoss(nn.Module):
         # ("terms steps") instead of sending the whole network to the module path; models.py sets it from the preset
         # key `terms_engine`
         self.terms_engine = False
+        # (no constructor arguments either) the feature-histogram term: models.py sets them from the preset keys of the same names
+        self.hist_loss_factor = 0.0
+        self.hist_loss_bins = 256
+        self.hist_loss_knots = 1024
         self.gram = GramMatrix()
         self.crit = _MseFn.apply
         self.loss = 0
@@ -345,6 +378,7 @@ class StyleLoss(nn.Module):
         self._shift_dropped = set()  # deltas some capture pass produced and another did not
         self._shift_named = set()
         self.flip_targets = {}  # mirror kind (0 = LR, 1 = UD, 2 = point mirror) -> (C, C): sum of blend weight x mirrored Gram
+        self.hist_target = None  # (C, hist_loss_knots): sum of blend weight x quantile table of the style's activation
         self.guided_target = None  # (R, C, C): sum over the style images of blend weight x guided Gram, per region
         self.guided_weight = None  # R blend-weight sums over the style images in which the region is active
         self._guided_ready = None
@@ -426,6 +460,8 @@ class StyleLoss(nn.Module):
                 raise NotImplementedError("StyleLoss: guides and shift_factor > 0 together are not implemented")
             if self.flip_factor > 0 or self.rotation_factor > 0:
                 raise NotImplementedError("StyleLoss: guides and flip_factor / rotation_factor > 0 together are not implemented")
+            if self.hist_loss_factor > 0:
+                raise NotImplementedError("StyleLoss: guides and hist_loss_factor > 0 together are not implemented")
             self.guided_loss(input)
             return input
         self.static_loss(input)
@@ -453,11 +489,15 @@ class StyleLoss(nn.Module):
                     t = self._shift_terms(frame, t)
                 if self.mirror_kinds():
                     t = self._flip_terms(frame, t)
+                if self.hist_loss_factor > 0:
+                    t = self._hist_terms(frame, t)
                 self.loss += self._accumulate(t) * self.strength / frames
             if self.mode == "capture" and self.shift_factor > 0:
                 self._shift_capture(frame, frames)
             if self.mode == "capture" and self.mirror_kinds():
                 self._flip_capture(frame, frames)
+            if self.mode == "capture" and self.hist_loss_factor > 0:
+                self._hist_capture(frame, frames)
 
     # -- long-range consistency (shift_factor > 0): G_s of loss.shift_deltas(H, W) along x and y, matched like the static Gram matrix
     def _shift_grams(self, frame, deltas):
@@ -528,6 +568,21 @@ class StyleLoss(nn.Module):
             factor = self.rotation_factor if kind == MIRROR_180 else self.flip_factor
             t = t + factor * self.crit(grams[i], self.flip_targets[kind])
         return t
+
+    # -- feature histograms (hist_loss_factor > 0): every channel matched to the blended quantile table of the style images
+    def _hist_capture(self, frame, frames):
+        contrib = self.blend_weight * hip.feat_hist_quantiles(frame, int(self.hist_loss_knots)) / frames
+        if self.hist_target is not None and self.hist_target.shape != contrib.shape:
+            raise ValueError("feature histograms: hist_loss_knots changed between two capture passes")
+        self.hist_target = contrib if self.hist_target is None else self.hist_target + contrib
+
+    def _hist_terms(self, frame, t):
+        if self.hist_target is None:
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: feature-histogram target not captured")
+        if tuple(self.hist_target.shape) != (frame.shape[1], int(self.hist_loss_knots)):
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: feature-histogram target of shape {tuple(self.hist_target.shape)} for "
+                               f"{frame.shape[1]} channels and {int(self.hist_loss_knots)} knots: capture again")
+        return t + self.hist_loss_factor * _FeatHistFn.apply(frame, self.hist_target, int(self.hist_loss_bins))
 
     def dynamic_loss(self, input):
         rows = input.shape[0] * input.shape[1]

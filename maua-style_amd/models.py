@@ -775,6 +775,10 @@ def assemble(features, layer_list, args):
                 "style", style_losses)
             # preset key too: the shift / mirror terms of this module run inside the fused engine (engine.py "terms steps"), default off
             style_losses[-1].terms_engine = bool(int(getattr(args, "terms_engine", 0) or 0))
+            # preset keys: the feature-histogram term (loss.StyleLoss), default off
+            style_losses[-1].hist_loss_factor = float(getattr(args, "hist_loss_factor", 0) or 0)
+            style_losses[-1].hist_loss_bins = int(getattr(args, "hist_loss_bins", 256) or 256)
+            style_losses[-1].hist_loss_knots = int(getattr(args, "hist_loss_knots", 1024) or 1024)
             found_style = True
         return found_content, found_style
 

@@ -65,10 +65,20 @@ def _mirrored(net_or_losses):
     return any(isinstance(m, loss_mod.StyleLoss) and bool(m.mirror_kinds()) for m in mods)
 
 
-def _terms_on_module_path(net_or_losses):
-    """The reason a shifted or mirrored network stays on the module path, or None: a style module with shift_factor > 0, or with a mirror
-    in use, whose `terms_engine` is off (the default).  With it on the fused engine evaluates those terms (engine.py, "terms steps")."""
+def _histogrammed(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) have hist_loss_factor > 0?  Such a network runs on the module path,
+    whatever `terms_engine` says: the fused engine has no feature-histogram step."""
     mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(isinstance(m, loss_mod.StyleLoss) and getattr(m, "hist_loss_factor", 0) > 0 for m in mods)
+
+
+def _terms_on_module_path(net_or_losses):
+    """The reason a shifted, mirrored or histogram-matched network stays on the module path, or None: a style module with
+    hist_loss_factor > 0, or one with shift_factor > 0 or a mirror in use whose `terms_engine` is off (the default).  With it on the fused
+    engine evaluates the shift and mirror terms (engine.py, "terms steps")."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    if _histogrammed(mods):
+        return "feature-histogram StyleLoss runs on the module path"
     style = [m for m in mods if isinstance(m, loss_mod.StyleLoss) and not getattr(m, "terms_engine", False)]
     if _shifted(style):
         return "shifted StyleLoss runs on the module path"
@@ -79,9 +89,10 @@ def _terms_on_module_path(net_or_losses):
 
 def _style_targets_missing(net):
     """A style module without its target - or, with shift_factor > 0, without its shift targets, or with a mirror in use without that
-    mirror's target (the factor was set after the capture)."""
+    mirror's target, or with hist_loss_factor > 0 without its quantile table (the factor was set after the capture)."""
     return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None)
-               or any(k not in m.flip_targets for k in m.mirror_kinds()) for m in net.style_losses)
+               or any(k not in m.flip_targets for k in m.mirror_kinds())
+               or (getattr(m, "hist_loss_factor", 0) > 0 and getattr(m, "hist_target", None) is None) for m in net.style_losses)
 
 
 def _engine_of(net):
