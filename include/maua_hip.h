@@ -445,6 +445,40 @@ int maua_feat_hist_fwd(const float* f, const float* table, void* state, float* l
 int maua_feat_hist_bwd(const float* f, const float* table, const void* state, const float* upstream, double coef, float* gx, int c, int h, int w,
                        int bins, int knots, int accumulate, maua_stream_t stream);
 
+/* ---- MRF patch-matching style loss: every 3x3 patch pulled towards its nearest style patch (mrf.hip) -------------- */
+/* Li & Wand 2016.  One frame f[C][h][w], h, w >= 3.  Query grid Hq = h - 2, Wq = w - 2, Q = Hq Wq, q = yq Wq + xq; the patch of query q is
+ * Psi_q(f)[c][dy][dx] = f[c][yq + dy][xq + dx], dy, dx in 0 .. 2.  A style bank is a map s[C][hs][ws] with origin[P] (int32, = ys ws + xs,
+ * the whole 3x3 patch inside the map) and inv[P] (fp32) = 1 / ||Psi_p(s)||, the squared norm summed in fp64 and rounded once; patches of
+ * norm 0 are never listed.
+ *     score(q, p) = inv[p] sum_{c,dy,dx} f[c][yq+dy][xq+dx] s[c][origin[p] + dy ws + dx]
+ *     nn[q]       = the p of the largest score; among bit-equal scores the lowest p  (the query's own norm does not change the arg-max)
+ *     loss        = 1 / (9 C Q) sum_q sum_{c,dy,dx} (f[c][yq+dy][xq+dx] - s[c][origin[nn[q]] + dy ws + dx])^2
+ *     gx[c][y][x] (+)= coef upstream[0] sum over (dy, dx) with 0 <= y - dy < Hq and 0 <= x - dx < Wq of
+ *                      (f[c][y][x] - s[c][origin[nn[(y-dy) Wq + (x-dx)]] + dy ws + dx])         (nn is a constant in the derivative)
+ * state: maua_mrf_state_bytes(h, w) bytes: nn[Q] (int32), then best[Q] (fp32, the winning score).
+ * maua_mrf_bank writes inv[0 .. P) on the device: once per capture.
+ * maua_mrf_fwd fills `state` and writes loss[0] (device, fp32), four launches.  Match: an implicit GEMM with K = 9 C on the fp32 matrix
+ *   cores; a workgroup owns 256 queries and one slice of the bank, keeps a running (score, p) per query in registers (strictly greater
+ *   wins, or equal with a lower p) and never writes the Q x P scores; the slices are a function of (Q, P) alone and a merging launch takes
+ *   their winners in slice order.  Loss: one gather pass that reads f once; partial sums go to the workspace and one workgroup adds them
+ *   in a fixed order in fp64.  No float atomics: the same inputs give the same bits.
+ *   workspace: maua_mrf_workspace_bytes(C, h, w, hs, ws, P) bytes, 8-byte aligned.
+ * maua_mrf_bwd: one launch, no workspace, a gather per element of gx (no scatter, no atomics); `state` as maua_mrf_fwd left it for the same
+ *   f and bank.  upstream: device fp32 scalar, NULL counts as 1; coef: host double (2 / (9 C Q) for the loss above).  With accumulate == 0
+ *   every element of gx is written.
+ * No element outside f, s, origin, inv and state is read; a padded query, a padded patch or a channel past C forms no address and can never
+ * win.  1 <= C <= 1024, h, w, hs, ws >= 3 with h w and hs ws below 2^30, 1 <= P <= 2^20; anything else returns MAUA_E_UNSUPPORTED (the
+ * queries: 0), null pointers MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before any launch.  An origin outside the map is the
+ * caller's error (hip.py checks the host tensor before upload). */
+int maua_mrf_supported(int c, int h, int w, int hs, int ws, int p);
+size_t maua_mrf_workspace_bytes(int c, int h, int w, int hs, int ws, int p);
+size_t maua_mrf_state_bytes(int h, int w);
+int maua_mrf_bank(const float* s, const int* origin, float* inv, int c, int hs, int ws, int p, maua_stream_t stream);
+int maua_mrf_fwd(const float* f, const float* s, const int* origin, const float* inv, void* state, float* loss, int c, int h, int w, int hs, int ws,
+                 int p, void* workspace, size_t workspace_bytes, maua_stream_t stream);
+int maua_mrf_bwd(const float* f, const float* s, const int* origin, const void* state, const float* upstream, double coef, float* gx, int c, int h,
+                 int w, int hs, int ws, int p, int accumulate, maua_stream_t stream);
+
 /* ---- shifted and mirrored Gram terms of the fused engine (gram_shift.hip, gram_flip.hip) ------------------------ */
 /* The two forward passes above with the MSE against per-term targets formed by their finishing launch, and the two backward passes with a
  * ReLU mask in their epilogue.  Arguments, limits and return codes are those of maua_gram_shift_fwd / _bwd and maua_gram_flip_fwd / _bwd;

@@ -123,6 +123,8 @@ class StyleEngine:
                     raise UnsupportedNet("mirrored StyleLoss runs on the module path")
                 if getattr(m, "hist_loss_factor", 0) > 0:  # (whatever `terms_engine` says: there is no feature-histogram step)
                     raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
+                if getattr(m, "mrf_factor", 0) > 0:  # (nor an MRF patch-matching step)
+                    raise UnsupportedNet("MRF patch-matching StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -584,6 +586,8 @@ class StyleEngine:
             return True
         if getattr(m, "hist_loss_factor", 0) > 0:  # (set after the engine was built: no engine evaluation without the term)
             raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
+        if getattr(m, "mrf_factor", 0) > 0:
+            raise UnsupportedNet("MRF patch-matching StyleLoss runs on the module path")
         td = getattr(self, "term_steps", {}).get(id(s)) if getattr(m, "terms_engine", False) else None
         if td is not None:
             if getattr(m, "guide", None) is not None:  # (as loss.StyleLoss.forward)

@@ -88,6 +88,12 @@ SIGNATURES = {
     "maua_feat_hist_state_bytes": (c_sz, [c_i, c_i]),
     "maua_feat_hist_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "maua_feat_hist_bwd": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_mrf_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "maua_mrf_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "maua_mrf_state_bytes": (c_sz, [c_i, c_i]),
+    "maua_mrf_bank": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "maua_mrf_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_mrf_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
@@ -1095,6 +1101,87 @@ def feat_hist_bwd(f, table, state, bins, coef, gx, accumulate, upstream=None):
     _check(lib().maua_feat_hist_bwd(_ptr(_f32(f, "f")), _ptr(_f32(table, "table")), state.data_ptr(), _ptr(_f32(upstream, "upstream")),
                                     float(coef), _ptr(_f32(gx, "gx")), c, h, w, int(bins), knots, int(accumulate), _stream()),
            "maua_feat_hist_bwd")
+    return gx
+
+
+def mrf_supported(c, h, w, hs, ws, p):
+    return bool(lib().maua_mrf_supported(int(c), int(h), int(w), int(hs), int(ws), int(p)))
+
+
+def mrf_workspace_bytes(c, h, w, hs, ws, p):
+    return lib().maua_mrf_workspace_bytes(int(c), int(h), int(w), int(hs), int(ws), int(p))
+
+
+def mrf_state_bytes(h, w):
+    return lib().maua_mrf_state_bytes(int(h), int(w))
+
+
+def mrf_state_parts(state, h, w):
+    """(nn (Q,) int32, best (Q,) float32) of a state maua_mrf_fwd filled, Q = (h - 2)(w - 2) (the layout of maua_hip.h)."""
+    q = (h - 2) * (w - 2)
+    return state[:q], state[q:2 * q].view(torch.float32)
+
+
+def mrf_bank(s, origin):
+    """The bank of one style map s (1,C,Hs,Ws) or (C,Hs,Ws) on the device: `origin` is a HOST int32 tensor (P,) of patch origins ys Ws + xs,
+    checked here - every 3x3 patch inside the map - before it is uploaded.  Returns (origin on the device, inv (P,) float32 =
+    1 / ||patch||).  Once per capture."""
+    c, hs, ws = s.shape[-3], s.shape[-2], s.shape[-1]
+    if s.numel() != c * hs * ws:
+        raise HipError("mrf_bank: s is one (C, Hs, Ws) map")
+    if origin.is_cuda or origin.dtype != torch.int32 or origin.dim() != 1:
+        raise HipError("mrf_bank: origin is a host int32 tensor (P,): it is checked before the upload")
+    p = origin.numel()
+    if not mrf_supported(c, 3, 3, hs, ws, p):
+        raise HipError(f"mrf_bank: {c} channels, a {hs} x {ws} style map, {p} patches are not supported")
+    o = origin.long()
+    if bool((o < 0).any()) or bool((o // ws > hs - 3).any()) or bool((o % ws > ws - 3).any()):
+        raise HipError(f"mrf_bank: an origin whose 3 x 3 patch leaves the {hs} x {ws} map")
+    od = origin.contiguous().to(s.device)
+    inv = torch.empty(p, dtype=torch.float32, device=s.device)
+    _check(lib().maua_mrf_bank(_ptr(_f32(s, "s")), od.data_ptr(), _ptr(inv), c, hs, ws, p, _stream()), "maua_mrf_bank")
+    return od, inv
+
+
+def _mrf_dims(who, f, s, origin, inv=None):
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    hs, ws = s.shape[-2], s.shape[-1]
+    p = origin.numel()
+    if f.numel() != c * h * w or s.numel() != c * hs * ws or origin.dtype != torch.int32 or not origin.is_cuda or not origin.is_contiguous() \
+            or (inv is not None and inv.numel() != p):
+        raise HipError(f"{who}: f is one (C, H, W) map, s one (C, Hs, Ws) map, origin a device int32 tensor (P,) and inv (P,)")
+    if not mrf_supported(c, h, w, hs, ws, p):
+        raise HipError(f"{who}: {c} channels, {h} x {w} pixels, a {hs} x {ws} style map, {p} patches are not supported")
+    return c, h, w, hs, ws, p
+
+
+def mrf_fwd(f, s, origin, inv, state=None, loss=None, workspace=None):
+    """f: (1,C,H,W) or (C,H,W); the bank (s, origin, inv) of mrf_bank.  Returns (loss (1,) float32 = the mean squared distance of every 3x3
+    patch to its nearest style patch, state): `state` (int32 words, mrf_state_bytes) holds nn[Q] and best[Q] - mrf_bwd reads nn."""
+    c, h, w, hs, ws, p = _mrf_dims("mrf_fwd", f, s, origin, inv)
+    words = mrf_state_bytes(h, w) // 4
+    if state is None:
+        state = torch.empty(words, dtype=torch.int32, device=f.device)
+    elif state.dtype != torch.int32 or state.numel() < words or not state.is_contiguous() or not state.is_cuda:
+        raise HipError("mrf_fwd: state is a contiguous int32 device tensor of mrf_state_bytes")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=f.device)
+    workspace = _ws(workspace, mrf_workspace_bytes(c, h, w, hs, ws, p), f.device)
+    _check(lib().maua_mrf_fwd(_ptr(_f32(f, "f")), _ptr(_f32(s, "s")), origin.data_ptr(), _ptr(_f32(inv, "inv")), state.data_ptr(),
+                              _ptr(_f32(loss, "loss")), c, h, w, hs, ws, p, workspace.data_ptr(),
+                              workspace.numel() * workspace.element_size(), _stream()), "maua_mrf_fwd")
+    return loss, state
+
+
+def mrf_bwd(f, s, origin, state, coef, gx, accumulate, upstream=None):
+    """gx (+)= coef upstream times, per element, the sum over the query patches that cover it of (f - the nearest style patch's value there);
+    state: what mrf_fwd left for the same f and bank; upstream: device float32 scalar or None (1)."""
+    c, h, w, hs, ws, p = _mrf_dims("mrf_bwd", f, s, origin)
+    if gx.numel() != f.numel() or state.dtype != torch.int32 or state.numel() < mrf_state_bytes(h, w) // 4 or not state.is_cuda \
+            or (upstream is not None and upstream.numel() != 1):
+        raise HipError("mrf_bwd: shapes of f, state, upstream and gx do not agree")
+    _check(lib().maua_mrf_bwd(_ptr(_f32(f, "f")), _ptr(_f32(s, "s")), origin.data_ptr(), state.data_ptr(), _ptr(_f32(upstream, "upstream")),
+                              float(coef), _ptr(_f32(gx, "gx")), c, h, w, hs, ws, p, int(accumulate), _stream()), "maua_mrf_bwd")
     return gx
 
 

@@ -24,6 +24,10 @@ DESIGN.md section 13).  Module path only, like the shift terms.
 Feature histograms (Risser, Wilmot & Barnes 2017): with `hist_loss_factor > 0` a StyleLoss also histogram-matches every channel of the
 activation to the style's channel and adds the mean squared distance to the matched map (csrc/feat_hist.hip) - the
 one term here that is not a second-order statistic.  Module path only.
+
+MRF patch matching (Li & Wand 2016): with `mrf_factor > 0` a StyleLoss also pulls every 3x3 patch of the activation towards its nearest
+style patch under normalised cross-correlation and adds the mean squared distance (csrc/mrf.hip) - the one term here
+that keeps local structure.  Module path only.
 """
 import sys
 
@@ -237,6 +241,51 @@ class _FeatHistFn(torch.autograd.Function):
         return gx, None, None
 
 
+class _MrfFn(torch.autograd.Function):
+    """m = mean over the queries q and (c, dy, dx) of (Psi_q(x) - Psi_nn[q](S))^2 for one frame x (1, C, H, W): nn[q] is the style patch of
+    the bank (s, origin, inv) with the largest normalised cross-correlation to the 3x3 patch Psi_q(x) (hip.mrf_fwd).  nn is a constant in
+    the derivative: backward is a gather per element, 2 / (9 C Q) times the incoming gradient (hip.mrf_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, s, origin, inv):
+        B, C, H, W = x.shape
+        if B != 1:
+            raise ValueError("MRF patch matching: one frame per call (B = 1)")
+        xc = x.contiguous()
+        loss, state = hip.mrf_fwd(xc, s, origin, inv)
+        ctx.save_for_backward(xc, s, origin, state)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, s, origin, state = ctx.saved_tensors
+        _, C, H, W = xc.shape
+        gx = torch.empty_like(xc)
+        hip.mrf_bwd(xc, s, origin, state, 2.0 / (9.0 * C * (H - 2) * (W - 2)), gx, False, upstream=g.reshape(1).float().contiguous())
+        return gx, None, None, None
+
+
+def mrf_grid(sizes, stride, max_patches):
+    """The patch grid of a bank over style maps of sizes [(Hs_i, Ws_i)], stacked along the height of one map as wide as the widest:
+    (s, origins) - s the smallest integer >= stride at which the grids of all maps together hold at most max_patches patches (a map of
+    Hs x Ws has ceil((Hs - 2) / s) ceil((Ws - 2) / s)), origins the host list of ys Ws + xs, map by map and row by row.  Every patch lies
+    within one map: none reaches into the next map or into a narrower map's padding."""
+    if not sizes or any(h < 3 or w < 3 for h, w in sizes):
+        raise ValueError(f"MRF patch matching: style activations of at least 3 x 3 are needed, got {sizes}")
+    if int(max_patches) < len(sizes):
+        raise ValueError(f"MRF patch matching: mrf_max_patches = {max_patches} for {len(sizes)} style maps")
+    ws = max(w for _, w in sizes)
+    s = max(1, int(stride))
+    while sum(-(-(h - 2) // s) * -(-(w - 2) // s) for h, w in sizes) > int(max_patches):
+        s += 1
+    origins, top = [], 0
+    for h, w in sizes:
+        for y in range(0, h - 2, s):
+            origins.extend((top + y) * ws + x for x in range(0, w - 2, s))
+        top += h
+    return s, origins
+
+
 class LayerGuides:
     """The guides of one style layer: `g` (R, H_l W_l) = the image-resolution guides resized to the activation with the project's bilinear
     kernel, `mass` N_r = sum g_r^2 (device, fp64; `mass_host` its one read-back), `active` = [N_r >= 1] and `scale` = 1 / (C N_r) on the
@@ -340,7 +389,10 @@ class StyleLoss(nn.Module):
     + rotation_factor mse(G_180, T_180): the shifted products of DESIGN.md section 12 and the mirrored ones of section 13.  `rotation_factor`
     drives the 180 degree term only; the paper's 90 degree terms (square maps, a transposing read) are not implemented.  With
     `hist_loss_factor > 0` the scalar also gains hist_loss_factor h, h the feature-histogram term of DESIGN.md section 15 (`hist_loss_bins`
-    bins, a target of `hist_loss_knots` quantiles per channel; use_covariance does not change it).  The dynamic term gets none of these."""
+    bins, a target of `hist_loss_knots` quantiles per channel; use_covariance does not change it).  With `mrf_factor > 0` it gains
+    mrf_factor m, m the MRF patch-matching term of DESIGN.md section 16: the bank holds the 3x3 patches of the style activations on a grid
+    of stride >= `mrf_stride`, at most `mrf_max_patches` of them.  Blend weights do not enter that term - a patch is matched or it is not -
+    except that a style image of blend weight 0 gives no patches; use_covariance does not change it.  The dynamic term gets none of these."""
 
     def __init__(self, strength, use_covariance=False, normalize=False, video_style_factor=0, shift_factor=0,
                  flip_factor=0, rotation_factor=0):
@@ -360,6 +412,10 @@ class StyleLoss(nn.Module):
         self.hist_loss_factor = 0.0
         self.hist_loss_bins = 256
         self.hist_loss_knots = 1024
+        # (nor here) the MRF patch-matching term: preset keys of the same names; models.py gives the factor to the layers of `mrf_layers`
+        self.mrf_factor = 0.0
+        self.mrf_stride = 2
+        self.mrf_max_patches = 16384
         self.gram = GramMatrix()
         self.crit = _MseFn.apply
         self.loss = 0
@@ -379,6 +435,8 @@ class StyleLoss(nn.Module):
         self._shift_named = set()
         self.flip_targets = {}  # mirror kind (0 = LR, 1 = UD, 2 = point mirror) -> (C, C): sum of blend weight x mirrored Gram
         self.hist_target = None  # (C, hist_loss_knots): sum of blend weight x quantile table of the style's activation
+        self.mrf_bank = None  # (S (C, Hs, Ws), origin (P,) int32, inv (P,)) on the device, built from _mrf_maps at the first evaluation
+        self._mrf_maps = []  # the captured style activations (C, Hs_i, Ws_i), in capture order
         self.guided_target = None  # (R, C, C): sum over the style images of blend weight x guided Gram, per region
         self.guided_weight = None  # R blend-weight sums over the style images in which the region is active
         self._guided_ready = None
@@ -462,6 +520,8 @@ class StyleLoss(nn.Module):
                 raise NotImplementedError("StyleLoss: guides and flip_factor / rotation_factor > 0 together are not implemented")
             if self.hist_loss_factor > 0:
                 raise NotImplementedError("StyleLoss: guides and hist_loss_factor > 0 together are not implemented")
+            if self.mrf_factor > 0:
+                raise NotImplementedError("StyleLoss: guides and mrf_factor > 0 together are not implemented")
             self.guided_loss(input)
             return input
         self.static_loss(input)
@@ -491,6 +551,8 @@ class StyleLoss(nn.Module):
                     t = self._flip_terms(frame, t)
                 if self.hist_loss_factor > 0:
                     t = self._hist_terms(frame, t)
+                if self.mrf_factor > 0:
+                    t = self._mrf_terms(frame, t)
                 self.loss += self._accumulate(t) * self.strength / frames
             if self.mode == "capture" and self.shift_factor > 0:
                 self._shift_capture(frame, frames)
@@ -498,6 +560,8 @@ class StyleLoss(nn.Module):
                 self._flip_capture(frame, frames)
             if self.mode == "capture" and self.hist_loss_factor > 0:
                 self._hist_capture(frame, frames)
+            if self.mode == "capture" and self.mrf_factor > 0:
+                self._mrf_capture(frame)
 
     # -- long-range consistency (shift_factor > 0): G_s of loss.shift_deltas(H, W) along x and y, matched like the static Gram matrix
     def _shift_grams(self, frame, deltas):
@@ -583,6 +647,47 @@ class StyleLoss(nn.Module):
             raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: feature-histogram target of shape {tuple(self.hist_target.shape)} for "
                                f"{frame.shape[1]} channels and {int(self.hist_loss_knots)} knots: capture again")
         return t + self.hist_loss_factor * _FeatHistFn.apply(frame, self.hist_target, int(self.hist_loss_bins))
+
+    # -- MRF patch matching (mrf_factor > 0): every 3x3 patch towards its nearest patch of the bank of all style images
+    def _mrf_capture(self, frame):
+        if self.blend_weight == 0:  # (an image that takes no part in the blend gives no patches)
+            return
+        self._mrf_maps.append(frame.detach()[0].float().contiguous().clone())
+        self.mrf_bank = None
+
+    def _mrf_build(self):
+        """The bank of the captured maps: stacked along the height, zero-padded to the widest, patches on loss.mrf_grid; a patch of norm 0
+        (maua_mrf_bank leaves inv = 0 for it) is not listed."""
+        maps = self._mrf_maps
+        C, ws = maps[0].shape[0], max(m.shape[2] for m in maps)
+        if any(m.shape[0] != C for m in maps):
+            raise ValueError("MRF patch matching: style activations of different channel counts")
+        smap = torch.zeros(C, sum(m.shape[1] for m in maps), ws, device=maps[0].device)
+        top = 0
+        for m in maps:
+            smap[:, top:top + m.shape[1], :m.shape[2]] = m
+            top += m.shape[1]
+        _, origins = mrf_grid([(m.shape[1], m.shape[2]) for m in maps], self.mrf_stride, self.mrf_max_patches)
+        origin = torch.tensor(origins, dtype=torch.int32)
+        _, inv = hip.mrf_bank(smap, origin)
+        keep = (inv > 0).cpu()
+        if not bool(keep.any()):
+            raise ValueError(f"{getattr(self, 'name', 'StyleLoss')}: every style patch of the MRF bank is zero")
+        if not bool(keep.all()):
+            origin = origin[keep].contiguous()
+        od, inv = hip.mrf_bank(smap, origin)  # (the same sums again for the patches kept: the same bits)
+        self.mrf_bank = (smap, od, inv)
+
+    def _mrf_terms(self, frame, t):
+        if self.mrf_bank is None:
+            if not self._mrf_maps:
+                raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: MRF patch bank not captured")
+            self._mrf_build()
+        smap, origin, inv = self.mrf_bank
+        if smap.shape[0] != frame.shape[1]:
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: MRF patch bank of {smap.shape[0]} channels for {frame.shape[1]}: "
+                               "capture again")
+        return t + self.mrf_factor * _MrfFn.apply(frame, smap, origin, inv)
 
     def dynamic_loss(self, input):
         rows = input.shape[0] * input.shape[1]

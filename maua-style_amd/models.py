@@ -742,6 +742,12 @@ def assemble(features, layer_list, args):
     Pure module plumbing - no tensor is touched, so it also runs without a GPU."""
     content_layers = args.content_layers.split(",")
     style_layers = args.style_layers.split(",")
+    # preset keys: the MRF patch-matching term (loss.StyleLoss, DESIGN.md section 16), default off; only the style layers named in
+    # `mrf_layers` (default: the paper's) get the factor
+    mrf_factor = float(getattr(args, "mrf_factor", 0) or 0)
+    mrf_layers = [n for n in str(getattr(args, "mrf_layers", None) or "relu3_1,relu4_1").split(",") if n]
+    if mrf_factor > 0 and any(n not in style_layers for n in mrf_layers):
+        raise ValueError(f"mrf_layers {mrf_layers} names a layer that is not a style layer: --style_layers is {style_layers}")
     features = copy.deepcopy(features)
     content_losses, style_losses, tv_losses, temporal_losses = [], [], [], []
     next_content_idx, next_style_idx = 1, 1
@@ -779,6 +785,9 @@ def assemble(features, layer_list, args):
             style_losses[-1].hist_loss_factor = float(getattr(args, "hist_loss_factor", 0) or 0)
             style_losses[-1].hist_loss_bins = int(getattr(args, "hist_loss_bins", 256) or 256)
             style_losses[-1].hist_loss_knots = int(getattr(args, "hist_loss_knots", 1024) or 1024)
+            style_losses[-1].mrf_factor = mrf_factor if layer_name in mrf_layers else 0.0
+            style_losses[-1].mrf_stride = int(getattr(args, "mrf_stride", 2) or 2)
+            style_losses[-1].mrf_max_patches = int(getattr(args, "mrf_max_patches", 16384) or 16384)
             found_style = True
         return found_content, found_style
 

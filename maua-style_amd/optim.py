@@ -72,6 +72,13 @@ def _histogrammed(net_or_losses):
     return any(isinstance(m, loss_mod.StyleLoss) and getattr(m, "hist_loss_factor", 0) > 0 for m in mods)
 
 
+def _patch_matched(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) have mrf_factor > 0?  Such a network runs on the module path,
+    whatever `terms_engine` says: the fused engine has no MRF patch-matching step."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(isinstance(m, loss_mod.StyleLoss) and getattr(m, "mrf_factor", 0) > 0 for m in mods)
+
+
 def _terms_on_module_path(net_or_losses):
     """The reason a shifted, mirrored or histogram-matched network stays on the module path, or None: a style module with
     hist_loss_factor > 0, or one with shift_factor > 0 or a mirror in use whose `terms_engine` is off (the default).  With it on the fused
@@ -79,6 +86,8 @@ def _terms_on_module_path(net_or_losses):
     mods = getattr(net_or_losses, "style_losses", net_or_losses)
     if _histogrammed(mods):
         return "feature-histogram StyleLoss runs on the module path"
+    if _patch_matched(mods):
+        return "MRF patch-matching StyleLoss runs on the module path"
     style = [m for m in mods if isinstance(m, loss_mod.StyleLoss) and not getattr(m, "terms_engine", False)]
     if _shifted(style):
         return "shifted StyleLoss runs on the module path"
@@ -92,7 +101,9 @@ def _style_targets_missing(net):
     mirror's target, or with hist_loss_factor > 0 without its quantile table (the factor was set after the capture)."""
     return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None)
                or any(k not in m.flip_targets for k in m.mirror_kinds())
-               or (getattr(m, "hist_loss_factor", 0) > 0 and getattr(m, "hist_target", None) is None) for m in net.style_losses)
+               or (getattr(m, "hist_loss_factor", 0) > 0 and getattr(m, "hist_target", None) is None)
+               or (getattr(m, "mrf_factor", 0) > 0 and getattr(m, "mrf_bank", None) is None and not getattr(m, "_mrf_maps", None))
+               for m in net.style_losses)
 
 
 def _engine_of(net):

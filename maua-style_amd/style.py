@@ -4,6 +4,8 @@
     torchrun --nproc-per-node 8 style.py --transfer_type vid_img --content frames/ --style S.png ...
     python style.py --content C.png --style S.png --load_args hist.json            (hist.json = {"hist_loss_factor": 1.0}: the feature-
         histogram term of Risser et al. 2017 in every style layer, loss.StyleLoss; further preset keys hist_loss_bins, hist_loss_knots)
+    python style.py --content C.png --style S.png --load_args mrf.json             (mrf.json = {"mrf_factor": 1.0}: the MRF patch-
+        matching term of Li & Wand 2016 on relu3_1 and relu4_1, loss.StyleLoss; further preset keys mrf_layers, mrf_stride, mrf_max_patches)
 
 `img_img` is the reference's coarse-to-fine loop (style.py:22-73): resume by file existence, bilinear rescaling of
 content / styles / previous result, optional histogram matching before and after every scale, optim.optimize per
