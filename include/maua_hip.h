@@ -479,6 +479,37 @@ int maua_mrf_fwd(const float* f, const float* s, const int* origin, const float*
 int maua_mrf_bwd(const float* f, const float* s, const int* origin, const void* state, const float* upstream, double coef, float* gx, int c, int h,
                  int w, int hs, int ws, int p, int accumulate, maua_stream_t stream);
 
+/* ---- sliced Wasserstein style loss: the feature-histogram match along D directions of feature space (swd.hip) ---- */
+/* Heitz, Vanhoey, Chambon & Belcour 2021.  One frame f[C][h w] (N = h w), directions dirs[D][C] (fp32, rows of unit length), a target
+ * table[D][knots] (the quantiles of the style's projections), `bins` histogram bins:
+ *     P = dirs f  (P[D][N], fp32 matrix cores, a fixed summation order: the same inputs give the same bits);
+ *     lo, hi, bin, counts, cum and the matched value R of P exactly as maua_feat_hist_fwd forms them for a map of D channels;
+ *     loss = sum over d, i of (P - R)^2 / (D N);    d loss / d f = 2 / (D N) dirs^T (P - R)    (R is a constant in the derivative).
+ * state: maua_swd_state_bytes(D, bins) bytes, the record of maua_feat_hist_fwd for D channels (lo, hi, cum[0 .. bins] per direction).
+ * workspace: maua_swd_workspace_bytes(C, D, h, w, bins, knots) bytes, 8-byte aligned; the same one for maua_swd_project and maua_swd_match.
+ * maua_swd_project writes proj[D][N] = P, one launch.  With state == NULL that is all (workspace and bins are not looked at): the
+ *   projection of a style map for its capture.  With a state it also writes the (min, max) of every workgroup's piece of every row of P to
+ *   slabs in the workspace and zeroes the bins + 1 counters of every direction in `state`, for the maua_swd_match that follows.
+ * maua_swd_match reads proj_inout = P, the slabs and the counters as maua_swd_project left them, fills `state`, writes loss[0] (device,
+ *   fp32) and overwrites proj_inout with G = P - R: four launches (counts, scan, residual, finish) that read P twice and write it once.
+ *   Integer global atomics for the counts, the partial sums of the loss in the workspace added by one workgroup in a fixed order in fp64;
+ *   no float atomics.  Between the two calls proj holds P and may be read.
+ * maua_swd_bwd: gx[C][N] (+)= coef * upstream[0] * dirs_t g, g[D][N] = G as maua_swd_match left it, dirs_t[C][D] the transpose of dirs.
+ *   upstream: device fp32 scalar, NULL counts as 1; coef: host double (2 / (D N) for the loss above).  With accumulate == 0 every element
+ *   of gx is written.  One launch, no workspace, no state.
+ * No element outside the named buffers is read or written: a row past D (or C), a pixel past N and a k past C (or D) form no address.
+ * 1 <= C, D <= 4096, h, w >= 1 with h w < 2^30, 16 <= bins <= 1024, 2 <= knots <= 4096; anything else returns MAUA_E_UNSUPPORTED (the
+ * queries: 0), null pointers MAUA_E_INVAL, a small workspace MAUA_E_WORKSPACE - all before any launch.  The queries need no GPU. */
+int maua_swd_supported(int c, int d, int h, int w, int bins, int knots);
+size_t maua_swd_workspace_bytes(int c, int d, int h, int w, int bins, int knots);
+size_t maua_swd_state_bytes(int d, int bins);
+int maua_swd_project(const float* f, const float* dirs, float* proj, void* state, int c, int d, int h, int w, int bins, void* workspace,
+                     size_t workspace_bytes, maua_stream_t stream);
+int maua_swd_match(float* proj_inout, const float* table, void* state, float* loss, int d, int h, int w, int bins, int knots, void* workspace,
+                   size_t workspace_bytes, maua_stream_t stream);
+int maua_swd_bwd(const float* g, const float* dirs_t, const float* upstream, double coef, float* gx, int c, int d, int h, int w, int accumulate,
+                 maua_stream_t stream);
+
 /* ---- shifted and mirrored Gram terms of the fused engine (gram_shift.hip, gram_flip.hip) ------------------------ */
 /* The two forward passes above with the MSE against per-term targets formed by their finishing launch, and the two backward passes with a
  * ReLU mask in their epilogue.  Arguments, limits and return codes are those of maua_gram_shift_fwd / _bwd and maua_gram_flip_fwd / _bwd;

@@ -125,6 +125,8 @@ class StyleEngine:
                     raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
                 if getattr(m, "mrf_factor", 0) > 0:  # (nor an MRF patch-matching step)
                     raise UnsupportedNet("MRF patch-matching StyleLoss runs on the module path")
+                if getattr(m, "swd_factor", 0) > 0:  # (nor a sliced Wasserstein step)
+                    raise UnsupportedNet("sliced-Wasserstein StyleLoss runs on the module path")
                 s = _Step("style", m)
                 s.src = act
             elif isinstance(m, models_mod.Conv2d):
@@ -588,6 +590,8 @@ class StyleEngine:
             raise UnsupportedNet("feature-histogram StyleLoss runs on the module path")
         if getattr(m, "mrf_factor", 0) > 0:
             raise UnsupportedNet("MRF patch-matching StyleLoss runs on the module path")
+        if getattr(m, "swd_factor", 0) > 0:
+            raise UnsupportedNet("sliced-Wasserstein StyleLoss runs on the module path")
         td = getattr(self, "term_steps", {}).get(id(s)) if getattr(m, "terms_engine", False) else None
         if td is not None:
             if getattr(m, "guide", None) is not None:  # (as loss.StyleLoss.forward)

@@ -94,6 +94,12 @@ SIGNATURES = {
     "maua_mrf_bank": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "maua_mrf_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "maua_mrf_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, ctypes.c_double, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "maua_swd_supported": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "maua_swd_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "maua_swd_state_bytes": (c_sz, [c_i, c_i]),
+    "maua_swd_project": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_swd_match": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "maua_swd_bwd": (c_i, [c_p, c_p, c_p, ctypes.c_double, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "maua_guided_gram_mse_ledger_supported": (c_i, [c_i, c_i]),
     "maua_guided_gram_fwd_mse_ledger": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "maua_guided_gram_bwd_masked": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i64, c_i, c_p]),
@@ -1182,6 +1188,88 @@ def mrf_bwd(f, s, origin, state, coef, gx, accumulate, upstream=None):
         raise HipError("mrf_bwd: shapes of f, state, upstream and gx do not agree")
     _check(lib().maua_mrf_bwd(_ptr(_f32(f, "f")), _ptr(_f32(s, "s")), origin.data_ptr(), state.data_ptr(), _ptr(_f32(upstream, "upstream")),
                               float(coef), _ptr(_f32(gx, "gx")), c, h, w, hs, ws, p, int(accumulate), _stream()), "maua_mrf_bwd")
+    return gx
+
+
+def swd_supported(c, d, h, w, bins, knots):
+    return bool(lib().maua_swd_supported(int(c), int(d), int(h), int(w), int(bins), int(knots)))
+
+
+def swd_workspace_bytes(c, d, h, w, bins, knots):
+    return lib().maua_swd_workspace_bytes(int(c), int(d), int(h), int(w), int(bins), int(knots))
+
+
+def swd_state_bytes(d, bins):
+    return lib().maua_swd_state_bytes(int(d), int(bins))
+
+
+def _swd_dims(who, f, dirs):
+    c, h, w = f.shape[-3], f.shape[-2], f.shape[-1]
+    if f.numel() != c * h * w or dirs.dim() != 2 or dirs.shape[1] != c:
+        raise HipError(f"{who}: f is one (C, H, W) map and dirs is (D, C)")
+    d = dirs.shape[0]
+    if not swd_supported(c, d, h, w, 16, 2):
+        raise HipError(f"{who}: {c} channels, {d} directions, {h} x {w} pixels are not supported")
+    return c, d, h, w
+
+
+def swd_project(f, dirs, bins=None, proj=None, state=None, workspace=None):
+    """f: (1,C,H,W) or (C,H,W); dirs: (D, C), rows of unit length.  Returns (P (D, H, W) = dirs f, state, workspace).  bins None: the plain
+    projection (state and workspace None) - the capture of a style map.  Otherwise `state` (int32 words, swd_state_bytes) has its counters
+    zeroed and `workspace` holds the range slabs of P: both go to the swd_match that follows."""
+    c, d, h, w = _swd_dims("swd_project", f, dirs)
+    if proj is None:
+        proj = torch.empty(d, h, w, dtype=torch.float32, device=f.device)
+    elif proj.numel() != d * h * w:
+        raise HipError("swd_project: proj is (D, H, W)")
+    if bins is None:
+        _check(lib().maua_swd_project(_ptr(_f32(f, "f")), _ptr(_f32(dirs, "dirs")), _ptr(_f32(proj, "proj")), None, c, d, h, w, 0, None, 0,
+                                      _stream()), "maua_swd_project")
+        return proj, None, None
+    if not swd_supported(c, d, h, w, bins, 2):
+        raise HipError(f"swd_project: {bins} bins are not supported")
+    words = swd_state_bytes(d, bins) // 4
+    if state is None:
+        state = torch.empty(words, dtype=torch.int32, device=f.device)
+    elif state.dtype != torch.int32 or state.numel() < words or not state.is_contiguous() or not state.is_cuda:
+        raise HipError("swd_project: state is a contiguous int32 device tensor of swd_state_bytes")
+    workspace = _ws(workspace, swd_workspace_bytes(c, d, h, w, bins, 2), f.device)
+    _check(lib().maua_swd_project(_ptr(_f32(f, "f")), _ptr(_f32(dirs, "dirs")), _ptr(_f32(proj, "proj")), state.data_ptr(), c, d, h, w,
+                                  int(bins), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+           "maua_swd_project")
+    return proj, state, workspace
+
+
+def swd_match(proj, table, state, bins, workspace, loss=None):
+    """proj: (D, H, W) = P, with `state` and `workspace` as swd_project left them; table: (D, knots).  Returns loss (1,) float32 = mean (P - R)^2
+    with R the matched projections; fills `state` (the feature-histogram record of P) and leaves G = P - R in `proj`."""
+    if proj.dim() != 3 or table.dim() != 2 or table.shape[0] != proj.shape[0]:
+        raise HipError("swd_match: proj is (D, H, W) and table is (D, knots)")
+    d, h, w = proj.shape
+    knots = table.shape[1]
+    if not swd_supported(1, d, h, w, bins, knots):
+        raise HipError(f"swd_match: {d} directions, {h} x {w} pixels, {bins} bins, {knots} knots are not supported")
+    if state.dtype != torch.int32 or state.numel() < swd_state_bytes(d, bins) // 4 or not state.is_contiguous() or not state.is_cuda:
+        raise HipError("swd_match: state is a contiguous int32 device tensor of swd_state_bytes")
+    if loss is None:
+        loss = torch.empty(1, dtype=torch.float32, device=proj.device)
+    _check(lib().maua_swd_match(_ptr(_f32(proj, "proj")), _ptr(_f32(table, "table")), state.data_ptr(), _ptr(_f32(loss, "loss")), d, h, w,
+                                int(bins), knots, workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+           "maua_swd_match")
+    return loss
+
+
+def swd_bwd(g, dirs_t, coef, gx, accumulate, upstream=None):
+    """gx (C, H, W) (+)= coef upstream dirs_t g; g: (D, H, W) as swd_match left it, dirs_t: (C, D) the transposed directions; upstream: device
+    float32 scalar or None (1)."""
+    if g.dim() != 3 or dirs_t.dim() != 2 or dirs_t.shape[1] != g.shape[0]:
+        raise HipError("swd_bwd: g is (D, H, W) and dirs_t is (C, D)")
+    d, h, w = g.shape
+    c = dirs_t.shape[0]
+    if gx.numel() != c * h * w or (upstream is not None and upstream.numel() != 1) or not swd_supported(c, d, h, w, 16, 2):
+        raise HipError("swd_bwd: shapes of g, dirs_t, upstream and gx do not agree")
+    _check(lib().maua_swd_bwd(_ptr(_f32(g, "g")), _ptr(_f32(dirs_t, "dirs_t")), _ptr(_f32(upstream, "upstream")), float(coef),
+                              _ptr(_f32(gx, "gx")), c, d, h, w, int(accumulate), _stream()), "maua_swd_bwd")
     return gx
 
 

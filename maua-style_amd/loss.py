@@ -28,6 +28,11 @@ one term here that is not a second-order statistic.  Module path only.
 MRF patch matching (Li & Wand 2016): with `mrf_factor > 0` a StyleLoss also pulls every 3x3 patch of the activation towards its nearest
 style patch under normalised cross-correlation and adds the mean squared distance (csrc/mrf.hip) - the one term here
 that keeps local structure.  Module path only.
+
+Sliced Wasserstein distance (Heitz, Vanhoey, Chambon & Belcour 2021): with `swd_factor > 0` a StyleLoss also projects the activation's feature
+vectors onto `swd_directions` fixed unit directions and matches every projection to the style's by monotone rearrangement - the feature-
+histogram match behind a rotation (csrc/swd.hip) - the one term here that constrains the joint distribution of the
+channels.  Module path only.
 """
 import sys
 
@@ -265,6 +270,41 @@ class _MrfFn(torch.autograd.Function):
         return gx, None, None, None
 
 
+def swd_directions(c, d, seed, index):
+    """The d directions of the style layer `index` (its position in net.style_losses) with c channels: (d, c) float32 on the CPU, rows of
+    unit length - a function of (seed, index, c, d) alone.  A CPU generator seeded with seed * 8191 + index draws randn(d, c) in fp64; the
+    rows are normalised in fp64 and rounded once.  These fp32 values are the directions for every user of them."""
+    gen = torch.Generator(device="cpu").manual_seed(int(seed) * 8191 + int(index))
+    v = torch.randn(int(d), int(c), dtype=torch.float64, generator=gen)
+    return (v / v.norm(dim=1, keepdim=True)).to(torch.float32)
+
+
+class _SwdFn(torch.autograd.Function):
+    """s = mean (P - R)^2 for one frame x (1, C, H, W): P = dirs x its projections onto the rows of `dirs` (D, C), R the projections matched,
+    direction by direction, to the quantile table `table` (D, knots) over `bins` bins.  hip.swd_project and hip.swd_match are looked up on
+    the module at every call (a test records P between them); the second leaves G = P - R in P's buffer, which is all the backward needs:
+    2 / (D H W) dirs^T G times the incoming gradient (hip.swd_bwd; `dirs_t` (C, D) is the transpose)."""
+
+    @staticmethod
+    def forward(ctx, x, dirs, dirs_t, table, bins):
+        B, C, H, W = x.shape
+        if B != 1:
+            raise ValueError("sliced Wasserstein distance: one frame per call (B = 1)")
+        xc = x.contiguous()
+        proj, state, workspace = hip.swd_project(xc, dirs, int(bins))
+        loss = hip.swd_match(proj, table, state, int(bins), workspace)
+        ctx.save_for_backward(proj, dirs_t)
+        ctx.shape = tuple(xc.shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        resid, dirs_t = ctx.saved_tensors
+        gx = torch.empty(ctx.shape, dtype=torch.float32, device=resid.device)
+        hip.swd_bwd(resid, dirs_t, 2.0 / resid.numel(), gx, False, upstream=g.reshape(1).float().contiguous())
+        return gx, None, None, None, None
+
+
 def mrf_grid(sizes, stride, max_patches):
     """The patch grid of a bank over style maps of sizes [(Hs_i, Ws_i)], stacked along the height of one map as wide as the widest:
     (s, origins) - s the smallest integer >= stride at which the grids of all maps together hold at most max_patches patches (a map of
@@ -392,7 +432,10 @@ class StyleLoss(nn.Module):
     bins, a target of `hist_loss_knots` quantiles per channel; use_covariance does not change it).  With `mrf_factor > 0` it gains
     mrf_factor m, m the MRF patch-matching term of DESIGN.md section 16: the bank holds the 3x3 patches of the style activations on a grid
     of stride >= `mrf_stride`, at most `mrf_max_patches` of them.  Blend weights do not enter that term - a patch is matched or it is not -
-    except that a style image of blend weight 0 gives no patches; use_covariance does not change it.  The dynamic term gets none of these."""
+    except that a style image of blend weight 0 gives no patches; use_covariance does not change it.  With `swd_factor > 0` it gains
+    swd_factor s, s the sliced Wasserstein term of DESIGN.md section 17 over `swd_directions` directions (0: as many as channels) drawn once
+    from `swd_seed` and the layer's `swd_index`, matched over `swd_bins` bins to a target of `swd_knots` quantiles per direction;
+    use_covariance does not change it.  The dynamic term gets none of these."""
 
     def __init__(self, strength, use_covariance=False, normalize=False, video_style_factor=0, shift_factor=0,
                  flip_factor=0, rotation_factor=0):
@@ -416,6 +459,13 @@ class StyleLoss(nn.Module):
         self.mrf_factor = 0.0
         self.mrf_stride = 2
         self.mrf_max_patches = 16384
+        # (nor here) the sliced Wasserstein term: preset keys of the same names; models.py also sets the layer's index among the style layers
+        self.swd_factor = 0.0
+        self.swd_directions = 0
+        self.swd_seed = 0
+        self.swd_bins = 256
+        self.swd_knots = 1024
+        self.swd_index = 0
         self.gram = GramMatrix()
         self.crit = _MseFn.apply
         self.loss = 0
@@ -437,6 +487,8 @@ class StyleLoss(nn.Module):
         self.hist_target = None  # (C, hist_loss_knots): sum of blend weight x quantile table of the style's activation
         self.mrf_bank = None  # (S (C, Hs, Ws), origin (P,) int32, inv (P,)) on the device, built from _mrf_maps at the first evaluation
         self._mrf_maps = []  # the captured style activations (C, Hs_i, Ws_i), in capture order
+        self.swd_target = None  # (D, swd_knots): sum of blend weight x quantile table of the style's projected activation
+        self._swd_dirs = None  # (V (D, C), V^T (C, D)) on the device, drawn at the first capture
         self.guided_target = None  # (R, C, C): sum over the style images of blend weight x guided Gram, per region
         self.guided_weight = None  # R blend-weight sums over the style images in which the region is active
         self._guided_ready = None
@@ -522,6 +574,8 @@ class StyleLoss(nn.Module):
                 raise NotImplementedError("StyleLoss: guides and hist_loss_factor > 0 together are not implemented")
             if self.mrf_factor > 0:
                 raise NotImplementedError("StyleLoss: guides and mrf_factor > 0 together are not implemented")
+            if self.swd_factor > 0:
+                raise NotImplementedError("StyleLoss: guides and swd_factor > 0 together are not implemented")
             self.guided_loss(input)
             return input
         self.static_loss(input)
@@ -553,6 +607,8 @@ class StyleLoss(nn.Module):
                     t = self._hist_terms(frame, t)
                 if self.mrf_factor > 0:
                     t = self._mrf_terms(frame, t)
+                if self.swd_factor > 0:
+                    t = self._swd_terms(frame, t)
                 self.loss += self._accumulate(t) * self.strength / frames
             if self.mode == "capture" and self.shift_factor > 0:
                 self._shift_capture(frame, frames)
@@ -562,6 +618,8 @@ class StyleLoss(nn.Module):
                 self._hist_capture(frame, frames)
             if self.mode == "capture" and self.mrf_factor > 0:
                 self._mrf_capture(frame)
+            if self.mode == "capture" and self.swd_factor > 0:
+                self._swd_capture(frame, frames)
 
     # -- long-range consistency (shift_factor > 0): G_s of loss.shift_deltas(H, W) along x and y, matched like the static Gram matrix
     def _shift_grams(self, frame, deltas):
@@ -688,6 +746,34 @@ class StyleLoss(nn.Module):
             raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: MRF patch bank of {smap.shape[0]} channels for {frame.shape[1]}: "
                                "capture again")
         return t + self.mrf_factor * _MrfFn.apply(frame, smap, origin, inv)
+
+    # -- sliced Wasserstein distance (swd_factor > 0): every projection matched to the blended quantile table of the styles' projections
+    def _swd_pair(self, frame):
+        """(V (D, C), V^T (C, D)) on the frame's device: loss.swd_directions of this layer, fixed until reset_targets()."""
+        C = frame.shape[1]
+        D = int(self.swd_directions) or C
+        if self._swd_dirs is None or tuple(self._swd_dirs[0].shape) != (D, C):
+            v = swd_directions(C, D, self.swd_seed, self.swd_index).to(frame.device)
+            self._swd_dirs = (v, v.t().contiguous())
+        return self._swd_dirs
+
+    def _swd_capture(self, frame, frames):
+        v, _ = self._swd_pair(frame)
+        proj, _, _ = hip.swd_project(frame.detach().float().contiguous(), v)
+        contrib = self.blend_weight * hip.feat_hist_quantiles(proj, int(self.swd_knots)) / frames
+        if self.swd_target is not None and self.swd_target.shape != contrib.shape:
+            raise ValueError("sliced Wasserstein distance: swd_directions or swd_knots changed between two capture passes")
+        self.swd_target = contrib if self.swd_target is None else self.swd_target + contrib
+
+    def _swd_terms(self, frame, t):
+        if self.swd_target is None:
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: sliced Wasserstein target not captured")
+        D = int(self.swd_directions) or frame.shape[1]
+        if tuple(self.swd_target.shape) != (D, int(self.swd_knots)):
+            raise RuntimeError(f"{getattr(self, 'name', 'StyleLoss')}: sliced Wasserstein target of shape {tuple(self.swd_target.shape)} for "
+                               f"{D} directions and {int(self.swd_knots)} knots: capture again")
+        v, vt = self._swd_pair(frame)
+        return t + self.swd_factor * _SwdFn.apply(frame, v, vt, self.swd_target, int(self.swd_bins))
 
     def dynamic_loss(self, input):
         rows = input.shape[0] * input.shape[1]

@@ -788,6 +788,14 @@ def assemble(features, layer_list, args):
             style_losses[-1].mrf_factor = mrf_factor if layer_name in mrf_layers else 0.0
             style_losses[-1].mrf_stride = int(getattr(args, "mrf_stride", 2) or 2)
             style_losses[-1].mrf_max_patches = int(getattr(args, "mrf_max_patches", 16384) or 16384)
+            # preset keys: the sliced Wasserstein term (loss.StyleLoss), default off; swd_directions 0 means as many
+            # directions as the layer has channels; the layer's index among the style layers seeds its directions
+            style_losses[-1].swd_factor = float(getattr(args, "swd_factor", 0) or 0)
+            style_losses[-1].swd_directions = int(getattr(args, "swd_directions", 0) or 0)
+            style_losses[-1].swd_seed = int(getattr(args, "swd_seed", 0) or 0)
+            style_losses[-1].swd_bins = int(getattr(args, "swd_bins", 256) or 256)
+            style_losses[-1].swd_knots = int(getattr(args, "swd_knots", 1024) or 1024)
+            style_losses[-1].swd_index = len(style_losses) - 1
             found_style = True
         return found_content, found_style
 

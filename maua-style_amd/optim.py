@@ -79,6 +79,13 @@ def _patch_matched(net_or_losses):
     return any(isinstance(m, loss_mod.StyleLoss) and getattr(m, "mrf_factor", 0) > 0 for m in mods)
 
 
+def _sliced(net_or_losses):
+    """Does a style module of the network (or of a list of loss modules) have swd_factor > 0?  Such a network runs on the module path,
+    whatever `terms_engine` says: the fused engine has no sliced Wasserstein step."""
+    mods = getattr(net_or_losses, "style_losses", net_or_losses)
+    return any(isinstance(m, loss_mod.StyleLoss) and getattr(m, "swd_factor", 0) > 0 for m in mods)
+
+
 def _terms_on_module_path(net_or_losses):
     """The reason a shifted, mirrored or histogram-matched network stays on the module path, or None: a style module with
     hist_loss_factor > 0, or one with shift_factor > 0 or a mirror in use whose `terms_engine` is off (the default).  With it on the fused
@@ -88,6 +95,8 @@ def _terms_on_module_path(net_or_losses):
         return "feature-histogram StyleLoss runs on the module path"
     if _patch_matched(mods):
         return "MRF patch-matching StyleLoss runs on the module path"
+    if _sliced(mods):
+        return "sliced-Wasserstein StyleLoss runs on the module path"
     style = [m for m in mods if isinstance(m, loss_mod.StyleLoss) and not getattr(m, "terms_engine", False)]
     if _shifted(style):
         return "shifted StyleLoss runs on the module path"
@@ -98,11 +107,12 @@ def _terms_on_module_path(net_or_losses):
 
 def _style_targets_missing(net):
     """A style module without its target - or, with shift_factor > 0, without its shift targets, or with a mirror in use without that
-    mirror's target, or with hist_loss_factor > 0 without its quantile table (the factor was set after the capture)."""
+    mirror's target, or with hist_loss_factor > 0 or swd_factor > 0 without its quantile table (the factor was set after the capture)."""
     return any(m.target.nelement() == 0 or (m.shift_factor > 0 and m.shift_target_deltas is None)
                or any(k not in m.flip_targets for k in m.mirror_kinds())
                or (getattr(m, "hist_loss_factor", 0) > 0 and getattr(m, "hist_target", None) is None)
                or (getattr(m, "mrf_factor", 0) > 0 and getattr(m, "mrf_bank", None) is None and not getattr(m, "_mrf_maps", None))
+               or (getattr(m, "swd_factor", 0) > 0 and getattr(m, "swd_target", None) is None)
                for m in net.style_losses)
 
 

@@ -6,6 +6,8 @@
         histogram term of Risser et al. 2017 in every style layer, loss.StyleLoss; further preset keys hist_loss_bins, hist_loss_knots)
     python style.py --content C.png --style S.png --load_args mrf.json             (mrf.json = {"mrf_factor": 1.0}: the MRF patch-
         matching term of Li & Wand 2016 on relu3_1 and relu4_1, loss.StyleLoss; further preset keys mrf_layers, mrf_stride, mrf_max_patches)
+    python style.py --content C.png --style S.png --load_args swd.json             (swd.json = {"swd_factor": 1.0}: the sliced Wasserstein
+        term of Heitz et al. 2021 in every style layer, loss.StyleLoss; further preset keys swd_directions, swd_seed, swd_bins, swd_knots)
 
 `img_img` is the reference's coarse-to-fine loop (style.py:22-73): resume by file existence, bilinear rescaling of
 content / styles / previous result, optional histogram matching before and after every scale, optim.optimize per
