@@ -5,13 +5,13 @@
 // Backward, D_m = dL/dG_m as given (not symmetrised):
 //     gx[c][q] (+)= sum_m coef_m sum_k (D_m[c][k] + D_m[k][c]) X[k][sigma_m(q)].
 //
-// Forward: gram_shift.hip's fp32-MFMA split-K kernel over the tile pairs ti <= tj only, with the mirror as the third grid dimension.  A stage
-// writes two operands to LDS, X at sigma(p) and X at p, zeros behind the plane's end; the finishing kernel adds the slabs in index order
-// (fp64), applies scale_m and writes (i, j) and (j, i) from the same sum - inside a diagonal tile from the triangle er <= ec only, since the
-// two triangles of an MFMA tile add their products in different orders.  The split of the pixel range depends on (C, H W) only, so a mirror
-// has the same bits alone or among others.
-// Backward: gs_bwd_kernel's layout (64 output channels x 256 pixels per workgroup, 32 input channels per double-buffered LDS stage), one run of
-// stages per mirror: the weight stage holds D_m[k][co] + D_m[co][k], added in registers before the LDS store.
+// The tiles, slabs, fp64 fold, ledger record and backward layout are gram_terms.hpp's (gf_bwd_kernel keeps its own text of the backward
+// pipeline, for speed: see there).  What this file plugs in:
+// Forward: the tile pairs ti <= tj only, the mirror as the term, int pixel indices (H W < 2^30).  A stage's operands are X at sigma(p) and
+// X at p, zeros behind the plane's end; the wave below the diagonal of a diagonal tile stages its share but multiplies nothing.  The finishing
+// kernels write (i, j) and (j, i) from the same sum - inside a diagonal tile from the triangle er <= ec only, since the two triangles of an
+// MFMA tile add their products in different orders.
+// Backward: one run of stages per mirror: the weight stage holds D_m[k][co] + D_m[co][k], added in registers before the LDS store.
 // The mirrored operand: sigma(p) descends as p ascends (LR, 180), so a pixel quad inside one row is the four consecutive addresses
 // sigma(p) - 3 .. sigma(p), one 16-byte load reversed in registers; UD reads whole rows ascending.  A quad that crosses a row end or the plane's
 // end goes element by element.  sigma(p) lies inside F exactly when p does: the mask of a quad (p < H W) is computed from indices first and
@@ -19,19 +19,12 @@
 // For the fused engine: a finishing kernel that also forms D_m = grad_scale_m (G_m - T_m) and the mirrors' loss as one ledger record
 // (gf_finish_mse_kernel), and a ReLU mask in the backward kernel's epilogue (gf_bwd_kernel's MASK flag).
 // hipcc-flags: -Xclang -target-feature -Xclang -packed-fp32-ops
-#include <stdlib.h>
-
-#include "fp16x3.hpp"
+#include "gram_terms.hpp"
 
 namespace maua {
 
-constexpr int GF_T = 64;         // tile edge (channels)
-constexpr int GF_K = 64;         // pixels per stage
-constexpr int GF_RS = GF_K + 4;  // LDS row stride (floats), as gram_shift.hip
-constexpr int GF_MMAX = 4;       // most mirrors per call
-constexpr int GF_KMAX = 768;     // most slabs per (mirror, tile pair): a single tile pair (C <= 64) still fills the device
-
-typedef float gf_f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int GF_MMAX = 4;    // most mirrors per call
+constexpr int GF_KMAX = 768;  // most slabs per (mirror, tile pair): a single tile pair (C <= 64) still fills the device
 
 struct GfMirrors {  // launch argument: the host arrays of one call
     int kind[GF_MMAX];
@@ -47,28 +40,13 @@ __device__ __forceinline__ unsigned gf_mask4(int p, int end) {
     return m;
 }
 
-// row[p + k] - mu for the elements k of the mask, 0 for the others; only the mask's addresses are formed
-__device__ __forceinline__ f32x4 gf_load4(const float* __restrict__ row, int p, unsigned m, float mu) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (m == 15u) {
-        v = *reinterpret_cast<const gf_f32x4u*>(row + p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] -= mu;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if ((m >> k) & 1u) v[k] = row[p + k] - mu;
-    }
-    return v;
-}
-
 // row[sigma(p + k)] - mu for the elements k of the mask (all of them below H W), 0 for the others.  (y, x) are the row and column of p.
 __device__ __forceinline__ f32x4 gf_load4_mirror(const float* __restrict__ row, int p, unsigned m, float mu, int kind, int H, int W, int y, int x) {
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     const int HW = H * W;
     if (m == 15u && (kind == 2 || x + 3 < W)) {  // the whole quad inside the plane and (LR, UD) inside one row: four consecutive addresses
         const int a = kind == 2 ? HW - 4 - p : kind == 0 ? y * W + (W - 4 - x) : (H - 1 - y) * W + x;
-        const f32x4 t = *reinterpret_cast<const gf_f32x4u*>(row + a);
+        const f32x4 t = *reinterpret_cast<const gt_f32x4u*>(row + a);
         if (kind == 1) {
             v = t;
         } else {
@@ -88,43 +66,30 @@ __device__ __forceinline__ f32x4 gf_load4_mirror(const float* __restrict__ row, 
     return v;
 }
 
-// the b-th pair (ti <= tj) of ntile tiles, rows first: (0,0) (0,1) .. (0,n-1) (1,1) ..
-__device__ __forceinline__ void gf_pair(int b, int ntile, int* ti, int* tj) {
-    int i = 0;
-    while (b >= ntile - i) {
-        b -= ntile - i;
-        ++i;
-    }
-    *ti = i;
-    *tj = i + b;
-}
-
 // One workgroup = one mirror x one 64x64 tile pair ti <= tj (ti: rows of G, the operand read at sigma(p); tj: columns, read at p) x one slice
-// of the plane; the four waves own a 32x32 block each.  Slabs: partial[((m npairs + pair) ksplit + ks) 64 64].
+// of the plane.
 __global__ void __launch_bounds__(256)
 gf_partial_kernel(const float* __restrict__ f, const float* __restrict__ mean, float* __restrict__ partial, GfMirrors mr, int C, int H, int W,
                   int npairs, int ksplit, int chunk) {
-    __shared__ __attribute__((aligned(16))) float At[GF_T * GF_RS];
-    __shared__ __attribute__((aligned(16))) float Bt[GF_T * GF_RS];
+    __shared__ __attribute__((aligned(16))) float At[GT_T * GT_RS];
+    __shared__ __attribute__((aligned(16))) float Bt[GT_T * GT_RS];
     const int s = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i32 = lane & 31, half = lane >> 5;
+    const int tid = threadIdx.x, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
-    const int ntile = (C + GF_T - 1) / GF_T;
     int ti, tj;
-    gf_pair(blockIdx.x, ntile, &ti, &tj);
+    gt_pair_upper(blockIdx.x, (C + GT_T - 1) / GT_T, &ti, &tj);
     const int ks = blockIdx.y;
     const int HW = H * W;  // below 2^30
     const int kind = mr.kind[s];
     const int p_begin = ks * chunk;  // ks chunk < H W + chunk
     const int p_end = min(HW, p_begin + chunk);
 
-    constexpr int NL = GF_T * GF_K / 4 / 256;  // 4 quads per tile per thread: rows tid / 16 + 16 q, pixels 4 (tid % 16) .. + 3
+    constexpr int NL = GT_T * GT_K / 4 / 256;
     const int r0 = tid >> 4, c4 = (tid & 15) * 4;
     float ma[NL], mb[NL];
 #pragma unroll
     for (int q = 0; q < NL; ++q) {
-        const int rowa = ti * GF_T + r0 + 16 * q, rowb = tj * GF_T + r0 + 16 * q;
+        const int rowa = ti * GT_T + r0 + 16 * q, rowb = tj * GT_T + r0 + 16 * q;
         ma[q] = (mean && rowa < C) ? mean[rowa] : 0.f;
         mb[q] = (mean && rowb < C) ? mean[rowb] : 0.f;
     }
@@ -135,102 +100,71 @@ gf_partial_kernel(const float* __restrict__ f, const float* __restrict__ mean, f
         const int y = pp / W, x = pp - y * W;
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            const int rowa = ti * GF_T + r0 + 16 * q, rowb = tj * GF_T + r0 + 16 * q;
+            const int rowa = ti * GT_T + r0 + 16 * q, rowb = tj * GT_T + r0 + 16 * q;
             ra[q] = gf_load4_mirror(f + (int64_t)min(rowa, C - 1) * HW, pp, rowa < C ? m : 0u, ma[q], kind, H, W, y, x);
-            rb[q] = gf_load4(f + (int64_t)min(rowb, C - 1) * HW, pp, rowb < C ? m : 0u, mb[q]);
+            rb[q] = gt_load4(f + (int64_t)min(rowb, C - 1) * HW, pp, rowb < C ? m : 0u, mb[q]);
         }
     };
     auto store_stage = [&]() {
 #pragma unroll
         for (int q = 0; q < NL; ++q) {
-            *reinterpret_cast<f32x4*>(At + (r0 + 16 * q) * GF_RS + c4) = ra[q];
-            *reinterpret_cast<f32x4*>(Bt + (r0 + 16 * q) * GF_RS + c4) = rb[q];
+            *reinterpret_cast<f32x4*>(At + (r0 + 16 * q) * GT_RS + c4) = ra[q];
+            *reinterpret_cast<f32x4*>(Bt + (r0 + 16 * q) * GT_RS + c4) = rb[q];
         }
     };
 
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-
+    f32x16 acc = gt_zero16();
     if (p_begin < p_end) {  // workgroup-uniform
         load_stage(p_begin);
-        for (int p0 = p_begin; p0 < p_end; p0 += GF_K) {
+        for (int p0 = p_begin; p0 < p_end; p0 += GT_K) {
             __syncthreads();  // previous stage fully consumed
             store_stage();
             __syncthreads();
-            if (p0 + GF_K < p_end) load_stage(p0 + GF_K);
+            if (p0 + GT_K < p_end) load_stage(p0 + GT_K);
             if (ti == tj && wi > wj) continue;  // (wave-uniform) the block below the diagonal of a diagonal tile is never read
-            const float* at = At + (wi * 32 + i32) * GF_RS + 4 * half;
-            const float* bt = Bt + (wj * 32 + i32) * GF_RS + 4 * half;
-#pragma unroll
-            for (int q = 0; q < GF_K / 8; ++q) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(at + 8 * q);
-                const f32x4 b = *reinterpret_cast<const f32x4*>(bt + 8 * q);
-#pragma unroll
-                for (int cp = 0; cp < 4; ++cp) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cp], b[cp], acc, 0, 0, 0);
-            }
+            gt_mma_stage(At, Bt, acc);
         }
     }
-    float* out = partial + (((int64_t)s * npairs + blockIdx.x) * ksplit + ks) * (GF_T * GF_T);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        out[row * GF_T + wj * 32 + i32] = acc[r];
-    }
+    gt_store_slab(partial, s, npairs, ksplit, acc);
 }
 
-// grid (tile pairs, 16, M): every thread owns one element of the 64x64 tile, adds its slab values in index order (fp64), applies the mirror's
-// scale and writes the element and its transpose; in a diagonal tile the threads with er <= ec only.
+// grid (tile pairs, 16, M): every thread owns one element of the 64x64 tile, folds its slab values, applies the mirror's scale and writes
+// the element and its transpose; in a diagonal tile the threads with er <= ec only.
 __global__ void __launch_bounds__(256)
 gf_finish_kernel(const float* __restrict__ partial, float* __restrict__ gram, GfMirrors mr, int C, int npairs, int ksplit) {
     const int s = blockIdx.z;
-    const int ntile = (C + GF_T - 1) / GF_T;
     int ti, tj;
-    gf_pair(blockIdx.x, ntile, &ti, &tj);
-    const int e = blockIdx.y * 256 + threadIdx.x;
-    const int er = e / GF_T, ec = e % GF_T;
-    const int gi = ti * GF_T + er, gj = tj * GF_T + ec;
+    gt_pair_upper(blockIdx.x, (C + GT_T - 1) / GT_T, &ti, &tj);
+    const int e[1] = {(int)(blockIdx.y * 256 + threadIdx.x)};
+    const int er = e[0] / GT_T, ec = e[0] % GT_T;
+    const int gi = ti * GT_T + er, gj = tj * GT_T + ec;
     if (gi >= C || gj >= C || (ti == tj && er > ec)) return;
-    const float* base = partial + ((int64_t)s * npairs + blockIdx.x) * ksplit * (GF_T * GF_T) + e;
-    double sd = 0.0;
-    int k = 0;
-    for (; k + 15 < ksplit; k += 16) {  // sixteen loads in flight, the additions in the order of a plain loop
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = base[(int64_t)(k + u) * (GF_T * GF_T)];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) sd += (double)v[u];
-    }
-    for (; k < ksplit; ++k) sd += (double)base[(int64_t)k * (GF_T * GF_T)];
-    const float g = (float)(sd * mr.factor[s]);
+    double sd[1];
+    gt_fold<16>(gt_slabs(partial, s, npairs, ksplit), e, ksplit, sd);
+    const float g = (float)(sd[0] * mr.factor[s]);
     float* gm = gram + (int64_t)s * C * C;
     gm[(int64_t)gi * C + gj] = g;
     gm[(int64_t)gj * C + gi] = g;
 }
 
 // gf_finish_kernel and the MSE against the mirrors' targets in one launch: grid (tile pairs, 16 / FQ, M), every thread owns FQ elements of
-// the 64x64 tile (e = 256 (FQ blockIdx.y + u) + tid); in a diagonal tile the elements with er <= ec only are live.  Each live element's slab
-// values are added in index order in fp64 exactly as gf_finish_kernel adds them (the same bits; the other threads fold an element they do
-// not use, which keeps every load unconditional); the target elements - read on and above
-// the diagonal only - are requested first, so they arrive beside the slabs and not behind them, and the loads of the thread's FQ elements
-// for sixteen slabs are requested together.  D_m = grad_scale_m (G_m - T_m) is formed once per live element and written with its mirror
-// like G_m (bit-symmetric whatever the target holds below its diagonal); exact zeros for a mirror with grad_scale_m == 0.  The workgroup's
-// share of loss_scale_m sum (G_m - T_m)^2 - an element off the diagonal counts twice - is one partial sum of the call's ledger record
-// (scale 1): M x pairs x 16 / FQ partial sums, a fixed order, no atomics.  The host takes the smallest FQ of 1, 2, 4 whose partial sums fit
-// the record (gf_finish_split): three mirrors of 512 channels take FQ = 1 (1728 sums).
+// the 64x64 tile (e = 256 (FQ blockIdx.y + u) + tid); in a diagonal tile the elements with er <= ec only are live.  Each live element is
+// folded exactly as gf_finish_kernel folds it (the same bits; the other threads fold an element they do not use, which keeps every load
+// unconditional); the target elements - read on and above the diagonal only - are requested first, so they arrive beside the slabs and
+// not behind them.  D_m = grad_scale_m (G_m - T_m) is formed once per live element and written with its mirror like G_m (bit-symmetric
+// whatever the target holds below its diagonal); exact zeros for a mirror with grad_scale_m == 0.  The workgroup's share of loss_scale_m
+// sum (G_m - T_m)^2 - an element off the diagonal counts twice - is one partial sum of the call's ledger record: three mirrors of 512
+// channels take FQ = 1 (1728 sums).
 struct GfTerms {  // launch argument: the host coefficient arrays of one maua_flip_gram_fwd_mse_ledger call
     double loss[GF_MMAX], grad[GF_MMAX];
 };
-constexpr int GF_FQ_MAX = 4;  // most elements per thread: 16 / 4 workgroups per (mirror, tile pair)
 template <int FQ>
 __global__ void __launch_bounds__(256)
 gf_finish_mse_kernel(const float* __restrict__ partial, float* __restrict__ gram, GfMirrors mr, GfTerms tw, int C, int npairs, int ksplit,
                      const float* __restrict__ target, float* __restrict__ dmat, double* __restrict__ rec) {
-    __shared__ double scratch[16];
     const int s = blockIdx.z;
-    const int ntile = (C + GF_T - 1) / GF_T;
     int ti, tj;
-    gf_pair(blockIdx.x, ntile, &ti, &tj);
+    gt_pair_upper(blockIdx.x, (C + GT_T - 1) / GT_T, &ti, &tj);
     const double ls = tw.loss[s];
     const float gs = (float)tw.grad[s];
     const int64_t mat = (int64_t)s * C * C;
@@ -240,38 +174,17 @@ gf_finish_mse_kernel(const float* __restrict__ partial, float* __restrict__ gram
 #pragma unroll
     for (int u = 0; u < FQ; ++u) {
         e[u] = (blockIdx.y * FQ + u) * 256 + threadIdx.x;
-        const int er = e[u] / GF_T, ec = e[u] % GF_T;
-        gi[u] = ti * GF_T + er;
-        gj[u] = tj * GF_T + ec;
+        const int er = e[u] / GT_T, ec = e[u] % GT_T;
+        gi[u] = ti * GT_T + er;
+        gj[u] = tj * GT_T + ec;
         live[u] = gi[u] < C && gj[u] < C && !(ti == tj && er > ec);
         tg[u] = live[u] ? target[mat + (int64_t)gi[u] * C + gj[u]] : 0.f;
         // every thread folds some element of the slabs, so that the loads below carry no condition and stay in flight together: an element
         // below the diagonal of a diagonal tile folds its row's diagonal element (the cache lines its wave reads anyway; the sum is not used)
-        if (ti == tj && er > ec) e[u] = er * GF_T + er;
+        if (ti == tj && er > ec) e[u] = er * GT_T + er;
     }
-    const float* base = partial + ((int64_t)s * npairs + blockIdx.x) * ksplit * (GF_T * GF_T);
     double sd[FQ];
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) sd[u] = 0.0;
-    int k = 0;
-    for (; k + 15 < ksplit; k += 16) {  // 16 FQ loads in flight, each element's additions in the order of a plain loop
-        float v[FQ][16];
-#pragma unroll
-        for (int u = 0; u < FQ; ++u)
-#pragma unroll
-            for (int w = 0; w < 16; ++w) v[u][w] = base[(int64_t)(k + w) * (GF_T * GF_T) + e[u]];
-#pragma unroll
-        for (int u = 0; u < FQ; ++u)
-#pragma unroll
-            for (int w = 0; w < 16; ++w) sd[u] += (double)v[u][w];
-    }
-    for (; k < ksplit; ++k) {
-        float v[FQ];
-#pragma unroll
-        for (int u = 0; u < FQ; ++u) v[u] = base[(int64_t)k * (GF_T * GF_T) + e[u]];
-#pragma unroll
-        for (int u = 0; u < FQ; ++u) sd[u] += (double)v[u];
-    }
+    gt_fold<16>(gt_slabs(partial, s, npairs, ksplit), e, ksplit, sd);
     double sq = 0.0;
 #pragma unroll
     for (int u = 0; u < FQ; ++u) {
@@ -286,33 +199,22 @@ gf_finish_mse_kernel(const float* __restrict__ partial, float* __restrict__ gram
         dmat[low] = dv;
         if (ls != 0.0) sq += (gi[u] != gj[u] ? 2.0 : 1.0) * ((double)d * (double)d);
     }
-    sq = block_sum(sq, scratch);
-    if (threadIdx.x == 0) {
-        rec[2 + ((int64_t)s * npairs + blockIdx.x) * gridDim.y + blockIdx.y] = ls != 0.0 ? sq * ls : 0.0;
-        if (blockIdx.x == 0 && blockIdx.y == 0 && s == 0) {
-            rec[0] = (double)(gridDim.x * gridDim.y * gridDim.z);
-            rec[1] = 1.0;
-        }
-    }
+    gt_ledger_put(sq, s, npairs, rec, [&](double sum) { return ls != 0.0 ? sum * ls : 0.0; });
 }
 
-// Backward.  Workgroup = 64 output channels x 256 pixels, wave = 64 x 64 (2 x 2 accumulators), 32 input channels per LDS stage,
-// double-buffered (80 KB); the stages run over (mirror, channel block).  A mirror whose coef is 0 is left out.
-constexpr int GFB_KC = 32, GFB_PX = 256, GFB_CO = 64;
-
-// MASK: the sums (and what they were accumulated into) are written as 0 where relu_mask[c][p] <= 0 (gram_bwd_kernel's pre-masked gradients).
+// Backward: the stage runs are the mirrors.  A mirror whose coef is 0 is left out.
 template <bool ACC, bool MASK>
 __global__ void __launch_bounds__(256)
 gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const float* __restrict__ mean, const float* __restrict__ relu_mask,
               float* __restrict__ gx, GfMirrors mr, int M, int C, int H, int W) {
     extern __shared__ __attribute__((aligned(16))) float smem_f32[];  // 2 x (Xl[32][256] + Wl[32][64])
     float* smem = smem_f32;
-    constexpr int BUF = GFB_KC * GFB_PX + GFB_KC * GFB_CO;
+    constexpr int BUF = GTB_KC * GTB_PX + GTB_KC * GTB_CO;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, half = lane >> 5;
     const int HW = H * W;
-    const int p0 = blockIdx.x * GFB_PX;
-    const int co0 = blockIdx.y * GFB_CO;
+    const int p0 = blockIdx.x * GTB_PX;
+    const int co0 = blockIdx.y * GTB_CO;
     const int pq = p0 + 4 * (tid & 63);  // this thread's pixel quad in every stage (each wave's 64 lanes cover the 256 pixels)
     const unsigned mq = gf_mask4(pq, HW);  // from indices alone; sigma(q) lies inside F exactly when q does
     const int qy = pq / W, qx = pq - qy * W;
@@ -341,8 +243,8 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (co < C) {
                 const float* drow = dr + (int64_t)co * C;
-                if (kq + 4 <= C) {
-                    v = *reinterpret_cast<const gf_f32x4u*>(drow + kq);
+                if (kq + 4 <= C) {  // (int indices, as everywhere in this file: gt_load4_end compares in 64 bits)
+                    v = *reinterpret_cast<const gt_f32x4u*>(drow + kq);
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -357,17 +259,18 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
     };
     auto store_stage = [&](int buf) {
         float* xl = smem + buf * BUF;
-        float* wl = xl + GFB_KC * GFB_PX;
+        float* wl = xl + GTB_KC * GTB_PX;
 #pragma unroll
         for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(xl + (tid + 256 * i) * 4) = rx[i];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int e = tid + 256 * i;  // a wave's lanes hold 64 different co: conflict-free LDS columns
 #pragma unroll
-            for (int k = 0; k < 4; ++k) wl[(4 * (e >> 6) + k) * GFB_CO + (e & 63)] = rw[i][k];
+            for (int k = 0; k < 4; ++k) wl[(4 * (e >> 6) + k) * GTB_CO + (e & 63)] = rw[i][k];
         }
     };
-
+    // The pipeline and epilogue below are gt_bwd_run's, kept here in this file's own text: built through the shared template this kernel
+    // alone came out 2 - 7 % slower (profiles/refactor_gram_terms.md), with the same registers and MFMAs and a different schedule.
     f32x16 acc[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -380,7 +283,7 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
     int st = 0, k0 = 0;
     while (st < M && !((active >> st) & 1u)) ++st;
     auto advance = [&]() {
-        k0 += GFB_KC;
+        k0 += GTB_KC;
         if (k0 >= C) {
             k0 = 0;
             ++st;
@@ -397,15 +300,15 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
             const bool more = st < M;
             if (more) load_stage(st, k0);
             const float* xl = smem + cur * BUF;
-            const float* wl = xl + GFB_KC * GFB_PX;
+            const float* wl = xl + GTB_KC * GTB_PX;
 #pragma unroll
-            for (int kp = 0; kp < GFB_KC / 2; ++kp) {
+            for (int kp = 0; kp < GTB_KC / 2; ++kp) {
                 const int kk = 2 * kp + half;
                 float a[2], b[2];
 #pragma unroll
-                for (int t = 0; t < 2; ++t) a[t] = wl[kk * GFB_CO + t * 32 + j];
+                for (int t = 0; t < 2; ++t) a[t] = wl[kk * GTB_CO + t * 32 + j];
 #pragma unroll
-                for (int u = 0; u < 2; ++u) b[u] = xl[kk * GFB_PX + (wave * 2 + u) * 32 + j];
+                for (int u = 0; u < 2; ++u) b[u] = xl[kk * GTB_PX + (wave * 2 + u) * 32 + j];
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -448,32 +351,7 @@ gf_bwd_kernel(const float* __restrict__ d, const float* __restrict__ f, const fl
     }
 }
 
-// slabs per (mirror, tile pair) and their length in pixels: about 768 workgroups per mirror's matrix, slices of whole stages - a function of
-// (C, H W) alone
-static void gf_plan(int c, int64_t hw, int* npairs, int* ksplit, int* chunk) {
-    const int ntile = (c + GF_T - 1) / GF_T;
-    *npairs = ntile * (ntile + 1) / 2;
-    const int64_t stages = (hw + GF_K - 1) / GF_K;
-    int64_t want = (768 + *npairs - 1) / *npairs;
-    if (want > GF_KMAX) want = GF_KMAX;
-    if (want > stages) want = stages;
-    if (want < 1) want = 1;
-    const int64_t ch = ((hw + want - 1) / want + GF_K - 1) / GF_K * GF_K;
-    *chunk = (int)ch;
-    *ksplit = (int)((hw + ch - 1) / ch);
-}
-
-// elements per thread of gf_finish_mse_kernel: the smallest of 1, 2, 4 for which mirrors x pairs x 16 / FQ partial sums fit one ledger
-// record (0: not even GF_FQ_MAX does)
-static int gf_finish_split(int mirrors, int64_t npairs) {
-    for (int fq = 1; fq <= GF_FQ_MAX; fq *= 2)
-        if ((int64_t)mirrors * npairs * (GF_T * GF_T / 256 / fq) <= LEDGER_MAX) return fq;
-    return 0;
-}
-
-static bool gf_shape_ok(int mirrors, int c, int h, int w) {
-    return mirrors >= 1 && mirrors <= GF_MMAX && c >= 1 && c <= (1 << 16) && h >= 1 && w >= 1 && (int64_t)h * w < (1ll << 30);
-}
+static bool gf_shape_ok(int mirrors, int c, int h, int w) { return h >= 1 && w >= 1 && gt_shape_ok(mirrors, GF_MMAX, c, (int64_t)h * w); }
 
 // the host arrays of a call into a launch argument; 0, or the error code after set_error
 static int gf_pack(const char* who, const int* kinds, const double* factors, int mirrors, GfMirrors* out) {
@@ -500,9 +378,7 @@ int maua_gram_flip_supported(int mirrors, int c, int h, int w) { return gf_shape
 
 size_t maua_gram_flip_workspace_bytes(int mirrors, int c, int h, int w) {
     if (!gf_shape_ok(mirrors, c, h, w)) return 0;
-    int npairs, ksplit, chunk;
-    gf_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
-    return (size_t)mirrors * npairs * ksplit * GF_T * GF_T * sizeof(float);
+    return gt_plan(c, (int64_t)h * w, false, GF_KMAX).slab_bytes(mirrors);
 }
 
 // maua_gram_flip_fwd; with `mse` the finishing launch is gf_finish_mse_kernel
@@ -522,13 +398,12 @@ static int gf_forward(const char* who, const float* f, const float* mean, const 
     if (rc) return rc;
     MAUA_REQUIRE(!mse || maua_flip_gram_mse_ledger_supported(mirrors, c), MAUA_E_UNSUPPORTED,
                  "%s: %d mirrors of %d channels need more than %d partial sums", who, mirrors, c, LEDGER_MAX);
-    const size_t need = maua_gram_flip_workspace_bytes(mirrors, c, h, w);
+    const GtPlan p = gt_plan(c, (int64_t)h * w, false, GF_KMAX);
+    const size_t need = p.slab_bytes(mirrors);
     MAUA_REQUIRE(workspace_bytes >= need, MAUA_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-    int npairs, ksplit, chunk;
-    gf_plan(c, (int64_t)h * w, &npairs, &ksplit, &chunk);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gf_partial_kernel, dim3(npairs, ksplit, mirrors), dim3(256), 0, s, f, mean, (float*)workspace, mr, c, h, w, npairs, ksplit,
-                       chunk);
+    hipLaunchKernelGGL(gf_partial_kernel, dim3(p.npairs, p.ksplit, mirrors), dim3(256), 0, s, f, mean, (float*)workspace, mr, c, h, w, p.npairs,
+                       p.ksplit, (int)p.chunk);
     rc = check_launch("gf_partial_kernel");
     if (rc) return rc;
     if (mse) {
@@ -537,18 +412,12 @@ static int gf_forward(const char* who, const float* f, const float* mean, const 
             tw.loss[i] = i < mirrors ? mse->loss_scales[i] : 0.0;
             tw.grad[i] = i < mirrors ? mse->grad_scales[i] : 0.0;
         }
-        const int fq = gf_finish_split(mirrors, npairs);
-        auto finish = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(npairs, GF_T * GF_T / 256 / fq, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, tw, c,
-                               npairs, ksplit, mse->target, mse->dmat, mse->rec);
-        };
-        if (fq == 1) finish(gf_finish_mse_kernel<1>);
-        else if (fq == 2) finish(gf_finish_mse_kernel<2>);
-        else finish(gf_finish_mse_kernel<4>);
+        gt_launch_finish_mse(gf_finish_mse_kernel<1>, gf_finish_mse_kernel<2>, gf_finish_mse_kernel<4>, mirrors, p, s, (const float*)workspace, gram,
+                             mr, tw, c, p.npairs, p.ksplit, mse->target, mse->dmat, mse->rec);
         return check_launch("gf_finish_mse_kernel");
     }
-    hipLaunchKernelGGL(gf_finish_kernel, dim3(npairs, GF_T * GF_T / 256, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, c, npairs,
-                       ksplit);
+    hipLaunchKernelGGL(gf_finish_kernel, dim3(p.npairs, GT_T * GT_T / 256, mirrors), dim3(256), 0, s, (const float*)workspace, gram, mr, c, p.npairs,
+                       p.ksplit);
     return check_launch("gf_finish_kernel");
 }
 
@@ -560,20 +429,8 @@ static int gf_backward(const char* who, const float* d, const float* f, const fl
     GfMirrors mr;
     const int rc = gf_pack(who, kinds, coefs, mirrors, &mr);
     if (rc) return rc;
-    const int64_t hw = (int64_t)h * w;
-    constexpr size_t lds = 2ull * (GFB_KC * GFB_PX + GFB_KC * GFB_CO) * sizeof(float);
-    const dim3 grid((unsigned)((hw + GFB_PX - 1) / GFB_PX), (unsigned)((c + GFB_CO - 1) / GFB_CO));
-    auto launch = [&](auto kernel) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, (hipStream_t)stream, d, f, mean, relu_mask, gx, mr, mirrors, c, h, w);
-    };
-    if (relu_mask) {
-        if (accumulate) launch(gf_bwd_kernel<true, true>);
-        else launch(gf_bwd_kernel<false, true>);
-    } else {
-        if (accumulate) launch(gf_bwd_kernel<true, false>);
-        else launch(gf_bwd_kernel<false, false>);
-    }
+    gt_launch_bwd(gf_bwd_kernel<false, false>, gf_bwd_kernel<true, false>, gf_bwd_kernel<false, true>, gf_bwd_kernel<true, true>, accumulate != 0,
+                  relu_mask != nullptr, c, (int64_t)h * w, (hipStream_t)stream, d, f, mean, relu_mask, gx, mr, mirrors, c, h, w);
     return check_launch("gf_bwd_kernel");
 }
 
@@ -588,9 +445,7 @@ int maua_gram_flip_bwd(const float* d, const float* f, const float* mean, const 
 }
 
 int maua_flip_gram_mse_ledger_supported(int mirrors, int c) {
-    if (!gf_shape_ok(mirrors, c, 1, 1)) return 0;
-    const int64_t nt = (c + GF_T - 1) / GF_T;
-    return gf_finish_split(mirrors, nt * (nt + 1) / 2) != 0 ? 1 : 0;
+    return gf_shape_ok(mirrors, c, 1, 1) && gt_finish_split(mirrors, gt_pairs(c, false)) != 0 ? 1 : 0;
 }
 
 int maua_flip_gram_fwd_mse_ledger(const float* f, const float* mean, const int* kinds, const double* scales, float* gram, int mirrors, int c,
